@@ -115,6 +115,48 @@ def aggregate_fps(frames_per_rank, world, elapsed_max):
     return frames_per_rank * world / elapsed_max
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, li, eng, cfg, seed=0):
+    """--dump-outputs: what the LAST timed step handed its caller, as .npy files (float32 / float64) under ``out_dir``, so that
+    two builds can be compared output for output on identical inputs:
+      last_step_sampler.npy   float64 [4]: video time, token the session went on with, token the sampler chose, and the
+                              sampler's bf16-rounded probability of the frame-interval token
+      last_step_response.npy  float64 [n]: the greedy response ids of that step (EOS included; empty when it stayed silent)
+      last_step_kv.npy        float32 [L, 2, n_kv_heads, T, head_dim]: K and V of the positions that step appended to the
+                              session (the frame step and its response), every layer
+      last_step_kv_pos.npy    float64 [T]: the session positions of those rows (a seeded sample of them beyond 64 MB in all)"""
+    import numpy as np
+    import torch
+    from videollm_online_amd.trace import FRAME, RESPONSE
+    os.makedirs(out_dir, exist_ok=True)
+    frame = next(e for e in reversed(li.trace) if e.kind == FRAME)
+    resp = li.trace[-1] if li.trace[-1].kind == RESPONSE and li.trace[-1].video_time == frame.video_time else None
+    p = float(li._p_dev.item())
+    np.save(os.path.join(out_dir, "last_step_sampler.npy"), np.array([frame.video_time, frame.token, frame.sampled, p], dtype=np.float64))
+    np.save(os.path.join(out_dir, "last_step_response.npy"), np.array(resp.output_ids if resp else [], dtype=np.float64))
+    # the frame step is the logged step that left the session at the frame event's length; the last step appended [Lc, end)
+    end = len(li.past_key_values)
+    lc = next(Lc for Lc, n in reversed(li.step_log) if Lc + n == frame.kv_len)
+    hd = cfg.hidden_size // cfg.num_attention_heads
+    L, nkv = cfg.num_hidden_layers, cfg.num_key_value_heads
+    pos = np.arange(lc, end)
+    cap = DUMP_MAX_BYTES // (L * 2 * nkv * hd * 4) - 1
+    if len(pos) > cap:
+        pos = np.sort(np.random.default_rng(seed).choice(pos, cap, replace=False))
+    kv = torch.empty(L, 2, nkv, len(pos), hd, dtype=torch.float32, device=eng.device)
+    idx = torch.as_tensor(pos - lc, device=eng.device)
+    for layer in range(L):
+        for which in range(2):
+            for h in range(nkv):
+                kv[layer, which, h] = li.past_key_values.read_kv(layer, which, h, lc, end).float()[idx]
+    np.save(os.path.join(out_dir, "last_step_kv.npy"), kv.cpu().numpy())
+    np.save(os.path.join(out_dir, "last_step_kv_pos.npy"), pos.astype(np.float64))
+    log(f"dump: last timed step (t = {frame.video_time}s) -> {out_dir}: sampler, {len(resp.output_ids) if resp else 0} response ids, "
+        f"KV rows {lc}..{end - 1} ({len(pos)} kept)")
+
+
 def make_schedule(mode):
     if mode == "scheduled":
         return lambda i: (i % 10 == 9, 16)
@@ -368,10 +410,15 @@ def main():
                     help="N > 1: skip the extra tensor-parallel measurement (run in child processes after the replica run)")
     ap.add_argument("--tp-leg-steps", type=int, default=300)
     ap.add_argument("--tp-leg-timeout", type=float, default=200.0, help="deadline of EACH tensor-parallel child leg (rccl, p2p)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed (sampler decision, response ids, the KV rows it "
+                         "appended) as DIR/<name>.npy, rank 0; single-engine runs only (not --tp)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.dump_outputs and args.tp:
+        raise SystemExit("--dump-outputs reads the session of one engine: not available with --tp")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU), so that an N-GPU line can
         # never be a silent 1-GPU run
@@ -508,6 +555,8 @@ def main():
     n_launch, prof_ms, bytes_per_launch = prof_eng.profile_read()
     eng.profile_enable(0)
     empty_us = prof_eng.profile_calibrate()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, li, eng, cfg)
     # encode stage in isolation (HIP events on its own stream): ms/frame and fraction of the dense fp16 MFMA peak
     vit_ms = vit1_ms = None
     if rank == 0:

@@ -6,6 +6,10 @@ GPU box (no /root/reference there) can check the oracle and the engine against t
 
     PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py
 
+The fixtures are made under pin_cpu_numerics(), and tests/test_oracle_golden.py recomputes the
+oracle under it: the bf16 results are compared bit for bit, which holds on any x86 host only
+with that arithmetic pinned.
+
 Import recipe follows SURVEY.md Appendix A: transformers' lazy symbols are resolved
 first, then shims for ``peft`` (models/modeling_live.py:2 — never executed when
 is_training=False and no checkpoint) and ``torchvision.transforms.functional.normalize``
@@ -22,6 +26,22 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 REF = os.environ.get("VLO_REFERENCE", "/root/reference")
+
+
+# MKL's conditional numerical reproducibility: the same sgemm results on every x86 CPU (by default MKL picks its kernels by
+# CPU, and the fp32 vision tower then moves by ~1e-6 between hosts, enough to flip a bf16 rounding downstream).  MKL reads it
+# when it starts, so it must be in the environment before the process's first BLAS call.
+PINNED_ENV = {"MKL_CBWR": "COMPATIBLE"}
+
+
+def pin_cpu_numerics():
+    """CPU arithmetic that does not depend on the host: MKL in its reproducible mode (PINNED_ENV), oneDNN off (its bf16
+    GEMM kernels differ by ISA, AMX vs AVX512-BF16, and split reductions by thread count) and one thread."""
+    for k, v in PINNED_ENV.items():
+        if os.environ.get(k) != v:
+            raise RuntimeError(f"{k}={v} must be in the environment before MKL starts")
+    torch.backends.mkldnn.enabled = False
+    torch.set_num_threads(1)
 
 
 def import_reference():
@@ -91,7 +111,7 @@ def main():
     from oracle import vlo_oracle as O
     (LiveLlamaConfig, LiveLlamaForCausalLM, ref_fast_greedy_generate, ref_siglip_vision_encode,
      SiglipVisionConfig, SiglipVisionModel) = import_reference()
-    torch.set_num_threads(8)
+    pin_cpu_numerics()
     out_dir = os.path.join(os.path.dirname(HERE), "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
 
@@ -264,4 +284,5 @@ def make_eval_golden(O, LiveLlamaConfig, LiveLlamaForCausalLM, out_dir):
 
 
 if __name__ == "__main__":
+    os.environ.update(PINNED_ENV)          # before any BLAS call of this process
     main()
