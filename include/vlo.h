@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define VLO_ABI_VERSION 3
+#define VLO_ABI_VERSION 4
 
 enum {
     VLO_OK = 0,
@@ -84,7 +84,8 @@ typedef struct vlo_config {
     int32_t tp_rank, tp_size;
     /* storage of the streamed Llama projections (q/k/v/o, gate/up/down, lm_head): 0 = bf16; 1 = fp8 e4m3 with one fp32 scale
      * per output channel (BASELINE.json configs[4] "fp8 MFMA weights").  With 1, vlo_engine_load_weight takes those matrices as
-     * VLO_DT_FP8_E4M3 [N][K] plus "<name>_scale" f32 [N] (W ~= q * scale[n]); activations, KV and accumulation are unchanged. */
+     * VLO_DT_FP8_E4M3 [N][K] plus "<name>_scale" f32 [N] (W ~= q * scale[n]); activations and accumulation are unchanged, the KV cache
+     * follows kv_dtype below. */
     int32_t weight_dtype;
     /* X operands of the LONG-INPUT projections (>= 256 new tokens: teacher-forced evaluation, a long first prompt) on an engine with
      * weight_dtype = 1: 0 = bf16 (the e4m3 image is expanded to bf16 per GEMM, bf16 MFMA: the arithmetic of the live step); 1 = every X row
@@ -92,6 +93,12 @@ typedef struct vlo_config {
      * rate; own parity band: the oracle run with the same activation rule).  The live step (<= 16 rows) and the 64-token block path keep
      * bf16 activations either way. */
     int32_t prefill_act_dtype;
+    /* storage of the paged KV cache: 0 = bf16; 1 = OCP e4m3fn, one byte per K / V element (same page geometry, half the bytes), with one
+     * static fp32 scale per layer for K and one for V: "model.layers.{i}.self_attn.k_scale" / "v_scale" (f32, one element, finite and > 0;
+     * vLLM's names), loadable only on such an engine, 1.0 when not loaded.  Stored code = e4m3_rne(clamp(x / scale, -448, 448)) of the bf16
+     * value a bf16 engine stores (K after RoPE, V); attention expands the codes to bf16 exactly and folds the scales into the softmax scale
+     * (K) and the partial outputs (V); Q, P and the MFMAs stay bf16.  vlo_session_read_kv returns bf16(code * scale).  Any weight_dtype. */
+    int32_t kv_dtype;
 } vlo_config;
 
 /* ---- engine lifetime: replaces build_model_and_tokenizer(...)[0] + model.to('cuda')
@@ -183,7 +190,7 @@ int vlo_greedy_generate(vlo_session *s, const void *embeds_dev, int m, int eos_t
                         int64_t *out_ids_dev, int max_new, int force_len, int *n_written, void *stream);
 
 /* ---- introspection for tests / bench ------------------------------------------------ */
-/* copy the session's K or V for (layer, kv_head) tokens [t0,t1) to dst_dev bf16 [t1-t0, head_dim] */
+/* copy the session's K or V for (layer, kv_head) tokens [t0,t1) to dst_dev bf16 [t1-t0, head_dim] (kv_dtype = 1: bf16(code * scale)) */
 int vlo_session_read_kv(vlo_session *s, int layer, int which /*0=K,1=V*/, int kv_head, int64_t t0, int64_t t1,
                         void *dst_dev, void *stream);
 /* algorithmic bytes of a step with n new tokens at cache length Lc */

@@ -17,6 +17,7 @@ def main():
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--tokens", type=int, default=2048)
     ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"], help="KV cache storage (fp8: the prefill attention takes the chunk kernel)")
     ap.add_argument("--act", default="bf16", choices=["bf16", "fp8"], help="fp8 engines: X operand of the prefill GEMMs (EngineConfig.prefill_act_dtype; fp8 = native fp8 MFMA)")
     ap.add_argument("--gemm", action="store_true", help="time the W8A8 GEMM alone on the layer's four projection shapes (vlo_test_gemm_fp8) and exit")
     ap.add_argument("--tp", type=int, default=1, help="T logical tensor-parallel ranks on this one GPU (csrc/tp.hip::tp_prefill): the ranks' shards run one "
@@ -35,7 +36,8 @@ def main():
             _, _, _, us = test_gemm_fp8(x, q, s, iters=20)
             print(f"[fp8 mfma gemm] {name:8s} M {M} N {N} K {K}: {us:9.1f} us = {2.0 * M * N * K / us * 1e-6:7.1f} TFLOP/s")
         return
-    cfg = EngineConfig(**SHAPES[args.model], kv_pool_tokens=max(16384, 2 * args.tokens), weight_dtype=args.weight_dtype, prefill_act_dtype=args.act)
+    cfg = EngineConfig(**SHAPES[args.model], kv_pool_tokens=max(16384, 2 * args.tokens), weight_dtype=args.weight_dtype, prefill_act_dtype=args.act,
+                       kv_dtype=args.kv_dtype)
     if args.tp > 1:
         from videollm_online_amd.engine import TpGroup
         eng = TpGroup(cfg, args.tp)

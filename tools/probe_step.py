@@ -2,6 +2,7 @@
 pipeline variants selected by environment (each variant in its own process: the switches are read once).
 
     python tools/probe_step.py [--model llama-3-8b] [--iters 40]      # e.g. VLO_FIXUP=0 python tools/probe_step.py
+    python tools/probe_step.py --kv-dtype fp8 --lens 4096,15519,66000   # the e4m3 KV cache (EngineConfig.kv_dtype)
 """
 import argparse
 import os
@@ -32,10 +33,12 @@ def main():
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--weight-dtype", default="bf16")
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"))
     ap.add_argument("--lens", default="0,4096,12288", help="cache lengths to time at")
     ap.add_argument("--ns", default="1,11", help="new tokens per step")
     args = ap.parse_args()
-    cfg = EngineConfig(**SHAPES[args.model], kv_pool_tokens=65536, weight_dtype=args.weight_dtype)
+    lens = [int(v) for v in args.lens.split(",")]
+    cfg = EngineConfig(**SHAPES[args.model], kv_pool_tokens=max(65536, max(lens) + 4096), weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
     eng = Engine(cfg)
     random_llm_weights_to_engine(eng, cfg)
     eng.finalize()
@@ -43,10 +46,10 @@ def main():
     sess = eng.new_session()
     fill = torch.randn(64, H, device="cuda").bfloat16()
     tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("VLO_")) or "defaults"
-    for Lc in [int(v) for v in args.lens.split(",")]:
+    for Lc in lens:
         while sess.get_seq_length() < Lc:
             eng.llm_step(sess, fill, want_last=False)
-        print(f"[{tag}, {args.weight_dtype}] Lc~{Lc:6d}:  " + "  ".join(f"n={n}: {timed(eng, sess, torch.randn(n, H, device='cuda').bfloat16(), args.iters):.3f} ms"
+        print(f"[{tag}, {args.weight_dtype}, kv {args.kv_dtype}] Lc~{Lc:6d}:  " + "  ".join(f"n={n}: {timed(eng, sess, torch.randn(n, H, device='cuda').bfloat16(), args.iters):.3f} ms"
                                                    for n in [int(v) for v in args.ns.split(",")]), flush=True)
 
 

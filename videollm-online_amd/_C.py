@@ -8,7 +8,7 @@ import torch  # noqa: F401  — loads torch's bundled libamdhip64 first so libvl
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvlo.so")
 
-VLO_ABI_VERSION = 3
+VLO_ABI_VERSION = 4
 DT_F32, DT_BF16, DT_F16, DT_FP8_E4M3 = 0, 1, 2, 3
 
 
@@ -23,7 +23,7 @@ class VloConfig(C.Structure):
         ("vit_num_layers", C.c_int32), ("vit_num_heads", C.c_int32), ("vit_image_size", C.c_int32),
         ("vit_patch_size", C.c_int32), ("vit_ln_eps", C.c_float), ("pool_h", C.c_int32), ("pool_w", C.c_int32),
         ("kv_pool_tokens", C.c_int64), ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("weight_dtype", C.c_int32),
-        ("prefill_act_dtype", C.c_int32),
+        ("prefill_act_dtype", C.c_int32), ("kv_dtype", C.c_int32),
     ]
 
 

@@ -58,10 +58,11 @@ def build_model_and_tokenizer(*, is_training: bool = False, llm_pretrained: str 
                               set_vision_inside: bool = False, resume_from_checkpoint: str = "", frame_token_cls: bool = True,
                               frame_token_pooled=(3, 3), frame_num_tokens: int = 10, frame_token_interval: str = ",",
                               frame_resolution: int = 384, tokenizer_builder=None, kv_pool_tokens: int = 32768, device: int = 0,
-                              **_ignored):
+                              kv_cache_dtype: str = "bf16", **_ignored):
     """Keyword-compatible with ``build_model_and_tokenizer(is_training=False, set_vision_inside=True, **asdict(args))``
     (demo/inference.py:15): arguments that only matter for training (lora_*, finetune_modules, attn_implementation,
-    torch_dtype, stream_loss_weight, ...) are accepted and ignored."""
+    torch_dtype, stream_loss_weight, ...) are accepted and ignored.  ``kv_cache_dtype="fp8"`` stores the KV cache as e4m3 with the
+    checkpoint's static per-layer k_scale / v_scale (1.0 where it has none; EngineConfig.kv_dtype)."""
     if is_training:
         raise NotImplementedError("the HIP engine is inference-only (SURVEY.md §8: training is out of scope)")
     if not llm_pretrained or not os.path.isdir(llm_pretrained):
@@ -81,7 +82,8 @@ def build_model_and_tokenizer(*, is_training: bool = False, llm_pretrained: str 
                        num_key_value_heads=hf.get("num_key_value_heads", hf["num_attention_heads"]), vocab_size=hf["vocab_size"],
                        rope_theta=float(hf.get("rope_theta", rope.get("rope_theta", 10000.0))), rms_norm_eps=hf.get("rms_norm_eps", 1e-5),
                        vision_hidden_size=vit["hidden_size"] if vit else 1024, frame_num_tokens=frame_num_tokens,
-                       frame_token_pooled=tuple(frame_token_pooled or (3, 3)), vit=vit, kv_pool_tokens=kv_pool_tokens)
+                       frame_token_pooled=tuple(frame_token_pooled or (3, 3)), vit=vit, kv_pool_tokens=kv_pool_tokens,
+                       kv_dtype=kv_cache_dtype)
     lcfg = LiveConfig(frame_token_interval=frame_token_interval or "", frame_num_tokens=frame_num_tokens,
                       frame_token_cls=frame_token_cls, frame_token_pooled=list(frame_token_pooled or ()))
     if tokenizer_builder is None:

@@ -81,6 +81,11 @@ def _adapter_maps(adapter_dir: str):
 FP8_E4M3_MAX = 448.0
 
 
+def is_kv_scale(name: str) -> bool:
+    """a static per-layer KV-cache scale of an fp8-KV engine: model.layers.{i}.self_attn.k_scale / v_scale"""
+    return name.startswith("model.layers.") and name.endswith((".self_attn.k_scale", ".self_attn.v_scale"))
+
+
 def round_to_e4m3(x: torch.Tensor) -> torch.Tensor:
     """fp32 values in [-448, 448] rounded to the nearest OCP e4m3 value, ties to even, returned as fp32.  Written out with
     frexp / ldexp / round so that every device rounds alike (the first hardware run showed torch's own float -> float8
@@ -109,7 +114,8 @@ def merge_lora(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: float) 
 
 
 def iter_llm_weights(base_dir: str, adapter_dir: str | None = None, device: str = "cpu"):
-    """Yields (hf_name, bf16 tensor) for every Llama + connector weight, LoRA merged."""
+    """Yields (hf_name, bf16 tensor) for every Llama + connector weight, LoRA merged; a quantised checkpoint's static KV-cache scales
+    (model.layers.{i}.self_attn.k_scale / v_scale) come as they are stored, in fp32."""
     base = _TensorSource(base_dir)
     src = lora = extra = None
     scale = 1.0
@@ -123,6 +129,9 @@ def iter_llm_weights(base_dir: str, adapter_dir: str | None = None, device: str 
         if "rotary_emb.inv_freq" in k:
             continue
         W = base.get(k).to(device)
+        if is_kv_scale(k):
+            yield k, W.float()
+            continue
         mod = k[:-len(".weight")] if k.endswith(".weight") else None
         if lora and mod in lora:
             ab = lora[mod]
@@ -160,7 +169,10 @@ def load_engine_weights(engine, base_dir: str, adapter_dir: str | None = None, s
                         device: str | None = None):
     """Stream a real checkpoint into an (un-finalized) Engine; merges LoRA on `device` (default: the GPU)."""
     dev = device or str(engine.device)
+    fp8_kv = getattr(engine.cfg, "kv_dtype", "bf16") == "fp8"
     for name, t in iter_llm_weights(base_dir, adapter_dir, dev):
+        if is_kv_scale(name) and not fp8_kv:
+            continue                          # the scales of an fp8 KV cache mean nothing to a bf16 one
         engine.load_weight(name, t)
     if siglip_dir:
         for name, t in iter_vision_weights(siglip_dir, dev):

@@ -27,6 +27,7 @@ def main(argv=None):
     ap.add_argument("--adapter", default=None)
     ap.add_argument("--siglip", default=None)
     ap.add_argument("--tokenizer", default=None, help="HF tokenizer directory (with the live chat template installed)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16", help="KV cache storage (fp8: e4m3 with per-layer static scales)")
     args = ap.parse_args(argv)
 
     import torch
@@ -36,7 +37,7 @@ def main(argv=None):
     from .modeling_live import LiveModel
 
     cfg = EngineConfig(**B.LLM_SHAPES["llama-3-8b"], vision_hidden_size=1024, vit=B.VIT_SHAPE,
-                       kv_pool_tokens=64 + 11 * args.frames + 120 * (args.frames + 2) + 4096)
+                       kv_pool_tokens=64 + 11 * args.frames + 120 * (args.frames + 2) + 4096, kv_dtype=args.kv_dtype)
     eng = Engine(cfg, 0)
     if args.base:
         from .checkpoint import load_engine_weights

@@ -2,6 +2,8 @@
 // attn_chunk_kernel (llm_ops.hip) with VLO_ATTN_BX / BY / BZ / GX = blockIdx.x / .y / .z / gridDim.x, VLO_ATTN_EXIT = return
 // (the kernel bodies live in .inc files so that variants walking the same virtual grid can share them).
 // Expects in scope: template parameters HD, HPW; the kernel's parameters by name; `float4 *lds_o`.
+// VLO_ATTN_F8 = 1 (attn_chunk_f8_kernel): the pool holds e4m3 bytes (8-byte K / V^T pieces expanded to the bf16 fragments in registers),
+// `scale` already carries the layer's k_scale and `vscale` multiplies the partial output.
     constexpr int NKK = HD / 32, NDT = HD / 16;
     const int NHG = G / HPW;
     float *lds_ml = reinterpret_cast<float *>(lds_o + (size_t)(KS - 1) * NHG * HPW * NDT * 64);   // [(KS-1)*NHG][HPW][16][2]
@@ -41,35 +43,57 @@
         for (int dt = 0; dt < NDT; ++dt) O[h][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     const int qpos = (int)pos0 + min(qrow, n - 1);
-    const bf16_t *kbase = kv.k_pool + (size_t)layer * kv.layer_stride;
-    const bf16_t *vbase = kv.vt_pool + (size_t)layer * kv.layer_stride;
+#if VLO_ATTN_F8
+    typedef uint8_t kv_t;                                          // one e4m3 byte per element, same element offsets
+    typedef uint2 kraw_t;                                          // 8 bytes = one fragment before expansion
+#else
+    typedef bf16_t kv_t;
+    typedef frag_ab kraw_t;
+#endif
+    const kv_t *kbase = reinterpret_cast<const kv_t *>(kv.k_pool) + (size_t)layer * kv.layer_stride;
+    const kv_t *vbase = reinterpret_cast<const kv_t *>(kv.vt_pool) + (size_t)layer * kv.layer_stride;
 
     // K fragments are fetched one 32-key block AHEAD (register double buffer), so the HBM latency of block i+1 hides
     // behind the MFMAs / softmax of block i; V^T fragments of the current block are issued first thing in the
     // iteration and are only needed after QK^T + softmax.
-    auto load_k = [&](int kt0, frag_ab (&dst)[2][NKK]) {
+    auto load_k = [&](int kt0, kraw_t (&dst)[2][NKK]) {
         const int page = kv.page_table[kt0 / VLO_PAGE_TOKENS];
-        const bf16_t *kp = kbase + (size_t)page * kv.page_elems + ((size_t)kvh * VLO_PAGE_TOKENS + kt0 % VLO_PAGE_TOKENS) * HD;
+        const kv_t *kp = kbase + (size_t)page * kv.page_elems + ((size_t)kvh * VLO_PAGE_TOKENS + kt0 % VLO_PAGE_TOKENS) * HD;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int kk = 0; kk < NKK; ++kk)
-                dst[t][kk] = *reinterpret_cast<const frag_ab *>(kp + (size_t)(t * 16 + qrow) * HD + kk * 32 + qd * 8);
+                dst[t][kk] = *reinterpret_cast<const kraw_t *>(kp + (size_t)(t * 16 + qrow) * HD + kk * 32 + qd * 8);
     };
-    frag_ab kf[2][NKK], kn[2][NKK];
+    frag_ab kf[2][NKK];
+    kraw_t kn[2][NKK];
     const int kfirst = c0 + ks * 32;
+#if VLO_ATTN_F8
+    if (kfirst < c1) {
+        load_k(kfirst, kn);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = fp8x8_to_bf16(kn[t][kk]);
+    }
+#else
     if (kfirst < c1) load_k(kfirst, kf);
+#endif
     for (int kt0 = kfirst; kt0 < c1; kt0 += KS * 32) {
         const int page = kv.page_table[kt0 / VLO_PAGE_TOKENS];
         const int tok0 = kt0 % VLO_PAGE_TOKENS;
-        const bf16_t *vp = vbase + (size_t)page * kv.page_elems + ((size_t)kvh * HD) * VLO_PAGE_TOKENS + tok0;
-        frag_ab vf[NDT];
+        const kv_t *vp = vbase + (size_t)page * kv.page_elems + ((size_t)kvh * HD) * VLO_PAGE_TOKENS + tok0;
+        kraw_t vf[NDT];
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
-            const bf16_t *vr = vp + (size_t)(dt * 16 + qrow) * VLO_PAGE_TOKENS + qd * 4;
+            const kv_t *vr = vp + (size_t)(dt * 16 + qrow) * VLO_PAGE_TOKENS + qd * 4;
+#if VLO_ATTN_F8
+            vf[dt] = make_uint2(*reinterpret_cast<const unsigned *>(vr), *reinterpret_cast<const unsigned *>(vr + 16));
+#else
             const uint2 lo = *reinterpret_cast<const uint2 *>(vr);
             const uint2 hi = *reinterpret_cast<const uint2 *>(vr + 16);
             vf[dt] = __builtin_bit_cast(frag_ab, make_uint4(lo.x, lo.y, hi.x, hi.y));
+#endif
         }
         const bool more = kt0 + KS * 32 < c1;
         if (more) load_k(kt0 + KS * 32, kn);
@@ -111,14 +135,22 @@
             for (int dt = 0; dt < NDT; ++dt) {
                 f32x4 o = O[h][dt];
                 o[0] *= alpha; o[1] *= alpha; o[2] *= alpha; o[3] *= alpha;
+#if VLO_ATTN_F8
+                O[h][dt] = mfma_bf16(fp8x8_to_bf16(vf[dt]), pb, o);
+#else
                 O[h][dt] = mfma_bf16(vf[dt], pb, o);
+#endif
             }
         }
         if (more) {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
+#if VLO_ATTN_F8
+                for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = fp8x8_to_bf16(kn[t][kk]);
+#else
                 for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = kn[t][kk];
+#endif
         }
     }
 #pragma unroll
@@ -178,7 +210,11 @@
         }
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
+#if VLO_ATTN_F8
+            const f32x4 o = O[h][dt] * vscale;                     // sum_j p_j v_code_j v_scale
+#else
             const f32x4 o = O[h][dt];
+#endif
             *reinterpret_cast<float4 *>(part_o + row * HD + dt * 16 + qd * 4) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }

@@ -101,3 +101,17 @@ VLO_DEV void fp8x16_to_bf16(frag_ab raw, frag_ab &f0, frag_ab &f1) {
     f1 = __builtin_bit_cast(frag_ab, make_uint4(fp8x2_to_bf16x2<false>(u.z), fp8x2_to_bf16x2<true>(u.z),
                                                   fp8x2_to_bf16x2<false>(u.w), fp8x2_to_bf16x2<true>(u.w)));
 }
+// one fragment (8 e4m3 bytes) -> 8 bf16: the fp8 KV pool's K / V^T pieces (llm_ops.hip)
+VLO_DEV frag_ab fp8x8_to_bf16(uint2 u) {
+    return __builtin_bit_cast(frag_ab, make_uint4(fp8x2_to_bf16x2<false>(u.x), fp8x2_to_bf16x2<true>(u.x),
+                                                  fp8x2_to_bf16x2<false>(u.y), fp8x2_to_bf16x2<true>(u.y)));
+}
+// four values -> four OCP e4m3 bytes (byte r = value r): e4m3_rne(clamp(x / s, -448, 448)), the clamp-then-v_cvt_pk_fp8_f32 rule of
+// quantize_rows_fp8_kernel (prefill.hip).  The fp8 KV cache's quantiser (s = the layer's k_scale / v_scale).
+VLO_DEV unsigned fp8x4_quant(float a, float b, float c, float d, float s) {
+    a = fminf(fmaxf(a / s, -448.f), 448.f); b = fminf(fmaxf(b / s, -448.f), 448.f);
+    c = fminf(fmaxf(c / s, -448.f), 448.f); d = fminf(fmaxf(d / s, -448.f), 448.f);
+    const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, lo, true);
+}
+VLO_DEV float fp8_to_f32(unsigned byte) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)byte, false)[0]; }

@@ -70,8 +70,10 @@ struct vlo_engine {
     void *cos_tab = nullptr, *sin_tab = nullptr;
     int64_t max_positions = 0;
 
-    // paged KV pool
+    // paged KV pool (bf16, or one e4m3 byte per element when cfg.kv_dtype = 1)
     void *k_pool = nullptr, *vt_pool = nullptr;
+    std::vector<float> kv_scale_h;               // kv_dtype = 1: [layer][2] {k_scale, v_scale} as loaded (1.0 when not), device copy kv_scale
+    float *kv_scale = nullptr;
     int pool_pages = 0;
     int64_t page_elems = 0, layer_stride = 0;
     std::vector<int> free_pages;
@@ -132,10 +134,16 @@ struct vlo_session {
 
 int dev_alloc(void **p, size_t bytes);
 // helpers shared with tp.hip
-struct KvGeom;
 int ensure_pages(vlo_session *s, int64_t new_len, hipStream_t st);
 GemvArgs gemv_args(const PackedLinear &pl, const unsigned short *x, int ldx, int n_rows);
-KvGeom kv_geom(const vlo_session *s);
+KvPool kv_geom(const vlo_session *s);
+// the qkv projection's append target: sets a.kv (+ a.kv_scale) and returns the epilogue, EPI_ROPE or EPI_ROPE_F8
+inline int rope_epi(GemvArgs &a, const KvPool &kv) {
+    a.kv = kv;
+    if (kv.dtype != VLO_KV_FP8) return EPI_ROPE;
+    a.kv_scale = kv.scale;
+    return EPI_ROPE_F8;
+}
 int ensure_prefill_ws(vlo_session *s);                        // prefill-path workspaces of a session (sized for the engine's shard)
 bool prefill_ok(const vlo_engine *e);                         // do this engine's (shard) shapes take the prefill GEMMs
 // layer_proj: a decoder-layer projection (takes the native fp8 MFMA when the engine asks for it); false = the lm_head (bf16 activations always)

@@ -92,6 +92,7 @@ int vlo_engine_create(const vlo_config *cfg, int device, vlo_engine **out) {
     if (cfg->weight_dtype != 0 && cfg->weight_dtype != 1) return fail(VLO_E_INVALID, "weight_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
     if (cfg->prefill_act_dtype != 0 && !(cfg->prefill_act_dtype == 1 && cfg->weight_dtype == 1))
         return fail(VLO_E_INVALID, "prefill_act_dtype must be 0 (bf16), or 1 (fp8 e4m3 per-row-scaled, native fp8 MFMA) on an engine with weight_dtype = 1");
+    if (cfg->kv_dtype != VLO_KV_BF16 && cfg->kv_dtype != VLO_KV_FP8) return fail(VLO_E_INVALID, "kv_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
     if ((cfg->hidden_size & 31) || (cfg->intermediate_size & 31) || (cfg->vocab_size & 3))
         return fail(VLO_E_UNSUPPORTED, "hidden/intermediate must be multiples of 32, vocab of 4");
     const int T = cfg->tp_size > 1 ? cfg->tp_size : 1;
@@ -113,6 +114,7 @@ int vlo_engine_create(const vlo_config *cfg, int device, vlo_engine **out) {
     e->I_l = cfg->intermediate_size / T;
     e->V_l = cfg->vocab_size / T;
     if (e->cfg.kv_pool_tokens <= 0) e->cfg.kv_pool_tokens = 16384;
+    if (cfg->kv_dtype == VLO_KV_FP8) e->kv_scale_h.assign((size_t)cfg->num_layers * 2, 1.0f);
     ingest_create(e);
     *out = e;
     return VLO_OK;
@@ -140,6 +142,20 @@ int vlo_engine_load_weight(vlo_engine *e, const char *name, const void *data, in
     const std::string n(name);
     size_t numel = 1;
     for (int i = 0; i < ndim; ++i) numel *= (size_t)shape[i];
+    {   // static per-layer KV scales of an fp8 KV pool: "model.layers.{i}.self_attn.k_scale" / "v_scale" (vlo_config.kv_dtype)
+        int layer = -1, pos = 0;
+        char kv = 0;
+        if (sscanf(name, "model.layers.%d.self_attn.%c_scale%n", &layer, &kv, &pos) == 2 && pos == (int)n.size() && (kv == 'k' || kv == 'v')) {
+            if (e->cfg.kv_dtype != VLO_KV_FP8) return fail(VLO_E_INVALID, n + ": KV scales are accepted by an engine created with kv_dtype = 1");
+            if (layer < 0 || layer >= e->cfg.num_layers || dtype != VLO_DT_F32 || numel != 1)
+                return fail(VLO_E_INVALID, n + ": expected one f32 element of a layer < num_layers");
+            float v = 0.f;
+            HIP_TRY(hipMemcpy(&v, data, sizeof(float), hipMemcpyDefault));
+            if (!std::isfinite(v) || !(v > 0.f)) return fail(VLO_E_INVALID, n + ": the scale must be finite and > 0");
+            e->kv_scale_h[(size_t)layer * 2 + (kv == 'v')] = v;
+            return VLO_OK;
+        }
+    }
     // storage dtype inside the engine: LLM + connector bf16; ViT matmul weights f16, the rest of the ViT f32
     int ddt = VLO_DT_BF16;
     if (n == "rope.inv_freq") ddt = VLO_DT_F32;
@@ -367,7 +383,12 @@ int vlo_engine_finalize(vlo_engine *e) {
     {
         e->page_elems = (int64_t)e->nkv_l * VLO_PAGE_TOKENS * hd;
         e->layer_stride = e->page_elems * e->pool_pages;
-        const size_t bytes = (size_t)e->layer_stride * c.num_layers * 2;
+        const size_t bytes = (size_t)e->layer_stride * c.num_layers * (c.kv_dtype == VLO_KV_FP8 ? 1 : 2);   // element counts are the same
+        if (c.kv_dtype == VLO_KV_FP8) {        // scales not loaded stay 1.0 (vlo_engine_create)
+            if ((rc = dev_alloc((void **)&e->kv_scale, e->kv_scale_h.size() * sizeof(float)))) return rc;
+            e->owned.push_back(e->kv_scale);
+            HIP_TRY(hipMemcpy(e->kv_scale, e->kv_scale_h.data(), e->kv_scale_h.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
         if ((rc = dev_alloc(&e->k_pool, bytes))) return rc;
         if ((rc = dev_alloc(&e->vt_pool, bytes))) return rc;
         e->owned.push_back(e->k_pool);
@@ -396,7 +417,7 @@ double vlo_step_algorithmic_bytes(const vlo_engine *e, int64_t Lc, int n) {
         const double rows_per_layer = (c.num_heads + 2.0 * c.num_kv_heads) * hd + H + 2.0 * I + H;
         W = W / 2.0 + (rows_per_layer * c.num_layers + c.vocab_size) * 4.0;
     }
-    const double kv = 2.0 * c.num_layers * c.num_kv_heads * hd * 2.0;
+    const double kv = 2.0 * c.num_layers * c.num_kv_heads * hd * (c.kv_dtype == VLO_KV_FP8 ? 1.0 : 2.0);   // K + V bytes per token
     return W + kv * (double)(Lc + n) + kv * n + 2.0 * n * H * 2.0;
 }
 
@@ -512,9 +533,9 @@ int ensure_pages(vlo_session *s, int64_t new_len, hipStream_t st) {
     return VLO_OK;
 }
 
-KvGeom kv_geom(const vlo_session *s) {
+KvPool kv_geom(const vlo_session *s) {
     const vlo_engine *e = s->e;
-    KvGeom g;
+    KvPool g;
     g.k_pool = (unsigned short *)e->k_pool;
     g.vt_pool = (unsigned short *)e->vt_pool;
     g.page_table = s->page_table;
@@ -522,6 +543,8 @@ KvGeom kv_geom(const vlo_session *s) {
     g.page_elems = e->page_elems;
     g.num_kv_heads = e->nkv_l;
     g.head_dim = e->head_dim;
+    g.dtype = e->cfg.kv_dtype;
+    g.scale = e->kv_scale;
     return g;
 }
 
@@ -630,7 +653,7 @@ static int run_chunk(vlo_session *s, const unsigned short *src, int m, bool want
     const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads;
     int rc;
     if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-    const KvGeom kv = kv_geom(s);
+    const KvPool kv = kv_geom(s);
     HIP_TRY(copy_rows_launch(src, s->h, m, H, st));
     const float *prev = nullptr;
     int prev_ks = 0;
@@ -640,8 +663,9 @@ static int run_chunk(vlo_session *s, const unsigned short *src, int m, bool want
         {   // qkv
             GemvArgs a = gemv_args(L.qkv, s->x, H, m);
             a.out_bf16 = s->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.kv = kv; a.layer = l; a.num_heads = nh; a.pos0 = s->len;
-            HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, EPI_ROPE, st));
+            a.layer = l; a.num_heads = nh; a.pos0 = s->len;
+            const int epi = rope_epi(a, kv);
+            HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
         }
         HIP_TRY(attention_launch(s->q, kv, l, nh, s->len, m, s->part_o, s->part_ml, s->attn, st));
         int sq_parts;
@@ -711,7 +735,7 @@ static int run_block(vlo_session *s, const unsigned short *src, int m, bool want
     int rc;
     if ((rc = ensure_block_ws(s))) return rc;
     if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-    const KvGeom kv = kv_geom(s);
+    const KvPool kv = kv_geom(s);
     HIP_TRY(copy_rows_launch(src, s->bh, m, H, st));
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerWeights &L = e->layers[l];
@@ -719,8 +743,9 @@ static int run_block(vlo_session *s, const unsigned short *src, int m, bool want
         {   // qkv
             GemvArgs a = gemv_args(L.qkv, s->bx, H, m);
             a.out_bf16 = s->bq; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.kv = kv; a.layer = l; a.num_heads = nh; a.pos0 = s->len;
-            HIP_TRY(gemm64_launch(a, L.qkv.plan64, EPI_ROPE, st));
+            a.layer = l; a.num_heads = nh; a.pos0 = s->len;
+            const int epi = rope_epi(a, kv);
+            HIP_TRY(gemm64_launch(a, L.qkv.plan64, epi, st));
         }
         // one launch for the (up to four) 16-query sub-chunks; the keys of the whole block are already appended
         HIP_TRY(attention_launch(s->bq, kv, l, nh, s->len, m, s->part_o, s->part_ml, s->battn, st, 0));
@@ -886,7 +911,7 @@ static int run_prefill(vlo_session *s, const unsigned short *src, int m, bool wa
     int rc;
     if ((rc = ensure_prefill_ws(s))) return rc;
     if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-    const KvGeom kv = kv_geom(s);
+    const KvPool kv = kv_geom(s);
     HIP_TRY(copy_rows_launch(src, s->ph, m, H, st));
     auto gemm = [&](const unsigned short *X, const PackedLinear &pl, int N, int K, unsigned short *out, int ldo, int kind) -> int {
         return prefill_gemm(s, X, pl, m, N, K, out, ldo, kind, st);

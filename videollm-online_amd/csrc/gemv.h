@@ -13,9 +13,11 @@ enum {
     EPI_SWIGLU = 3,          // tile = 8 gate rows + 8 up rows of the same columns -> bf16(silu(g) * u)   (gate_up)
     EPI_RESID = 4,           // h[m][col] = bf16(h + bf16(acc)); per-row sum of squares partials (o_proj, down_proj)
     EPI_ROPE = 5,            // q/k/v split, RoPE, q buffer + paged K / V^T append   (qkv)
-    EPI_PARTIAL_MBOX = 6     // tensor parallel, ksplit == 1: a rank's o / down partial sums published as {epoch, fp32} granules straight into EVERY
+    EPI_PARTIAL_MBOX = 6,    // tensor parallel, ksplit == 1: a rank's o / down partial sums published as {epoch, fp32} granules straight into EVERY
                              // rank's p2p mailbox (tp.hip "p2p exchange"): no partial matrix in HBM, no publish pass in the exchange kernel
+    EPI_ROPE_F8 = 7          // EPI_ROPE appending to an fp8 e4m3 pool (llm_ops.h KvPool): K after RoPE and V quantised with kv_scale[layer]
 };
+constexpr bool epi_rope(int epi) { return epi == EPI_ROPE || epi == EPI_ROPE_F8; }
 // activation operand source
 enum {
     XSRC_PLAIN = 0,          // x is a bf16 [16][ldx] tile
@@ -27,7 +29,10 @@ struct GemvArgs {
     int wq;                       // 0: bf16 image;  1: fp8 e4m3 image + per-output-channel scales
     const float *wscale;          // wq: fp32 [NT * 16] in packed row order (row r of tile t at t * 16 + r)
     const unsigned short *x;      // XSRC_PLAIN: bf16 [16][ldx];  XSRC_NORM: residual stream h, bf16 [16][ldx]
-    float *out_f32;               // EPI_PARTIAL_F32
+    union {
+        float *out_f32;           // EPI_PARTIAL_F32
+        const float *kv_scale;    // EPI_ROPE_F8: the pool's [layer][2] {k_scale, v_scale} (KvPool::scale; the two epilogues never meet)
+    };
     unsigned short *out_bf16;     // EPI_BF16 / GELU / SWIGLU: [16][ldo];  EPI_ROPE: q buffer [16][nh*hd]
     const unsigned short *bias;   // bf16 [N] or null
     int K, ldx, ldo;

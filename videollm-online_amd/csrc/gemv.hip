@@ -171,7 +171,7 @@ int gemv_plan(int K, bool allow_ksplit, GemvPlan *p) {
 // groups of two column tiles, or single tiles when that balances better over the CUs (pairs are mandatory for the
 // rotary epilogue).  e.g. gate/up: 1792 tiles = 7.0 per CU as singles, 896 pairs = 3.5 -> 4 per CU (87.5 %).
 static bool single_tile_groups(const GemvArgs &a, const GemvPlan &p, int epi) {
-    if (epi == EPI_ROPE) return false;
+    if (epi_rope(epi)) return false;
     const int slots = 256 / p.ksplit > 0 ? 256 / p.ksplit : 1;
     auto eff = [&](int items) {
         const int rounds = (items + slots - 1) / slots;
@@ -180,7 +180,7 @@ static bool single_tile_groups(const GemvArgs &a, const GemvPlan &p, int epi) {
     return eff(a.NT) > eff((a.NT + 1) / 2) + 0.2;     // HBM saturates below 256 CUs: a 12 % idle-CU tail costs less than 2x the barriers
 }
 static int groups_of(const GemvArgs &a, const GemvPlan &p, int epi) {
-    if (epi == EPI_ROPE) return a.NT / 2;
+    if (epi_rope(epi)) return a.NT / 2;
     return single_tile_groups(a, p, epi) ? a.NT : (a.NT + 1) / 2;
 }
 
@@ -228,6 +228,7 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
         if (epi == EPI_SWIGLU) VLO_GO(XSRC_NORM, EPI_SWIGLU);
     } else {
         if (epi == EPI_ROPE) VLO_GO(XSRC_PLAIN, EPI_ROPE);
+        if (epi == EPI_ROPE_F8) VLO_GO(XSRC_PLAIN, EPI_ROPE_F8);
         if (epi == EPI_SWIGLU) VLO_GO(XSRC_PLAIN, EPI_SWIGLU);
         if (epi == EPI_RESID) VLO_GO(XSRC_PLAIN, EPI_RESID);
         if (epi == EPI_BF16) VLO_GO(XSRC_PLAIN, EPI_BF16);
@@ -242,7 +243,8 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
 hipError_t gemv_prepare(GemvArgs *a, const GemvPlan &p, int epi, int *grid_x, int *grid_y, size_t *lds_bytes) {
     if (epi != EPI_PARTIAL_F32 && p.ksplit != 1) return hipErrorInvalidValue;
     if (epi == EPI_PARTIAL_MBOX && (a->mbox_T < 1 || a->mbox_T > 8 || !a->mbox[0])) return hipErrorInvalidValue;
-    if (epi == EPI_ROPE && ((a->NT & 1) || (a->kv.head_dim != 64 && a->kv.head_dim != 128))) return hipErrorInvalidValue;
+    if (epi == EPI_ROPE_F8 && !a->kv_scale) return hipErrorInvalidValue;
+    if (epi_rope(epi) && ((a->NT & 1) || (a->kv.head_dim != 64 && a->kv.head_dim != 128))) return hipErrorInvalidValue;
     a->CT = single_tile_groups(*a, p, epi) ? 1 : 2;
     a->KC = p.KC;
     *grid_x = gemv_grid_x(*a, p, epi);

@@ -6,7 +6,7 @@
         __syncthreads();
 
         // ---- cross-wave reduction + epilogue ------------------------------------------------
-        if (EPI == EPI_ROPE) {
+        if (epi_rope(EPI)) {
             // both tiles of the group are needed by the same lane (rotary pair): one wave
             if (threadIdx.x < 64) {
                 const int l = lane;
@@ -46,8 +46,30 @@
                                 lo[r] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
                                 hi[r] = f2bf(rbf(x2 * c) + rbf(x1 * s));
                             }
-                            *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
-                            *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
+                            if (EPI == EPI_ROPE_F8 && head >= nh) {
+                                // fp8 pool: the bf16 K row quantised with the layer's k_scale, 4 + 4 bytes
+                                const float ks = a.kv_scale[2 * a.layer];
+                                uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.k_pool) + (size_t)a.layer * a.kv.layer_stride +
+                                              (size_t)page * a.kv.page_elems + ((size_t)(head - nh) * VLO_PAGE_TOKENS + tok) * hd;
+                                *reinterpret_cast<unsigned *>(d8 + i) = fp8x4_quant(bf2f(lo[0]), bf2f(lo[1]), bf2f(lo[2]), bf2f(lo[3]), ks);
+                                *reinterpret_cast<unsigned *>(d8 + half + i) = fp8x4_quant(bf2f(hi[0]), bf2f(hi[1]), bf2f(hi[2]), bf2f(hi[3]), ks);
+                            } else {
+                                *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
+                                *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
+                            }
+                        } else if (EPI == EPI_ROPE_F8) {
+                            // fp8 V^T: this lane's 4 + 4 head-dim rows of one token are bytes VLO_PAGE_TOKENS apart; the 16 lanes of a row hold
+                            // 16 consecutive tokens, so each byte store of the wave covers 16 adjacent bytes
+                            const float vs = a.kv_scale[2 * a.layer + 1];
+                            uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.vt_pool) + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
+                                          ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;
+                            const unsigned ca = fp8x4_quant(rbf(va[0]), rbf(va[1]), rbf(va[2]), rbf(va[3]), vs);
+                            const unsigned cb = fp8x4_quant(rbf(vb[0]), rbf(vb[1]), rbf(vb[2]), rbf(vb[3]), vs);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                d8[(size_t)(i + r) * VLO_PAGE_TOKENS] = (uint8_t)(ca >> (8 * r));
+                                d8[(size_t)(half + i + r) * VLO_PAGE_TOKENS] = (uint8_t)(cb >> (8 * r));
+                            }
                         } else {
                             bf16_t *dst = a.kv.vt_pool + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
                                           ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;

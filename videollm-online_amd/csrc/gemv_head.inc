@@ -14,13 +14,13 @@
 
     // ---- group -> tiles -----------------------------------------------------------------
     const int hd = a.kv.head_dim;
-    const int tph = (EPI == EPI_ROPE) ? hd / 16 : 2;           // tiles per head
+    const int tph = epi_rope(EPI) ? hd / 16 : 2;           // tiles per head
     const int hp = tph / 2;                                    // rotary pairs of tiles per head
     // a.CT == 1: one tile per group (narrow outputs such as o_proj: NT = 256 tiles -> 256 blocks instead of 128)
-    const bool single = (EPI != EPI_ROPE && a.CT == 1);
-    const int ngroups = (EPI == EPI_ROPE) ? a.NT / 2 : (single ? a.NT : (a.NT + 1) / 2);
-    auto tile_a = [&](int g) { return (EPI == EPI_ROPE) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
-    auto tile_b = [&](int g) { return (EPI == EPI_ROPE) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
+    const bool single = (!epi_rope(EPI) && a.CT == 1);
+    const int ngroups = epi_rope(EPI) ? a.NT / 2 : (single ? a.NT : (a.NT + 1) / 2);
+    auto tile_a = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
+    auto tile_b = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
 
     constexpr int WRN = WQ ? KF / 2 : KF;                      // 16-byte weight registers per chunk (KiB in flight per wave)
     const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ ? kfw0 / 2 : kfw0) * 64 + lane;

@@ -18,6 +18,16 @@ struct KvGeom {
     int num_kv_heads, head_dim;
 };
 
+// KV storage formats (vlo_config.kv_dtype)
+enum { VLO_KV_BF16 = 0, VLO_KV_FP8 = 1 };
+// Host-side view of a session's pool: the geometry every kernel takes (KvGeom, whose layout the bf16 kernels' ISA depends on) plus the
+// storage format.  VLO_KV_FP8: k_pool / vt_pool hold one OCP e4m3 byte per element at the SAME element offsets (layer_stride and page_elems
+// count elements), and `scale` is the device array [layer][2] = {k_scale, v_scale}; code = e4m3_rne(clamp(x / scale, -448, 448)).
+struct KvPool : KvGeom {
+    int dtype = VLO_KV_BF16;
+    const float *scale = nullptr;
+};
+
 // "packed-64" activation layout of the 64-token block path (prefill.hip): the B-operand fragments of
 // v_mfma_f32_16x16x32_bf16 stored contiguously, so one fragment load is one coalesced 1 KiB read instead of 16 half-used
 // cache lines of a row-major matrix.  Element (row < 64, k) lives at
@@ -39,13 +49,14 @@ hipError_t add_rmsnorm_launch(unsigned short *h, const float *partial, int kspli
 // part_cap: capacity of part_o / part_ml in (16-query sub-chunk x split) partial states of [nh][16][hd] / [nh][16][2] floats: the
 // session's buffers hold VLO_MAX_SPLITS (n <= 64); the prefill path brings VLO_PREFILL_TOKENS / 16 and runs a whole block of new
 // tokens as ONE launch (grid.z = its 16-query sub-chunks, one split each)
-hipError_t attention_launch(const unsigned short *q, KvGeom kv, int layer, int num_heads, int64_t pos0, int n,
+hipError_t attention_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n,
                             float *part_o, float *part_ml, unsigned short *out, hipStream_t st, int pack_row0 = -1, int part_cap = VLO_MAX_SPLITS);
 
 // flash-style attention for a block of n new tokens at positions pos0 .. pos0 + n - 1 whose keys are already appended (prefill path):
 // out bf16 [n][nh * hd] row-major.  hipErrorNotSupported for GQA shapes it is not instantiated for (the caller uses attention_launch).
-bool attention_prefill_supported(int head_dim, int gqa_group);      // is attn_prefill_kernel instantiated for this shape (else attention_prefill_launch returns hipErrorNotSupported)
-hipError_t attention_prefill_launch(const unsigned short *q, KvGeom kv, int layer, int num_heads, int64_t pos0, int n, unsigned short *out,
+// The flash kernels read bf16 pools only: an fp8 pool takes attention_launch.
+bool attention_prefill_supported(int head_dim, int gqa_group, int kv_dtype);   // is attn_prefill_kernel instantiated for this shape (else attention_prefill_launch returns hipErrorNotSupported)
+hipError_t attention_prefill_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n, unsigned short *out,
                                     hipStream_t st);
 
 // launch geometry of the chunk attention for n new tokens at cache length pos0 (what attention_launch computes first)
@@ -68,7 +79,7 @@ struct StepIds { int64_t v[VLO_STEP_IDS_MAX]; };      // token ids handed to ste
 hipError_t step_input_launch(const unsigned short *table, const StepIds &ids, int k, const unsigned short *frame_rows, int rows, int H,
                              int64_t vocab, unsigned short *out, hipStream_t st);
 hipError_t copy_rows_launch(const unsigned short *src, unsigned short *dst, int rows, int H, hipStream_t st);
-hipError_t read_kv_launch(KvGeom kv, int layer, int which, int kv_head, int64_t t0, int64_t t1, unsigned short *dst,
+hipError_t read_kv_launch(const KvPool &kv, int layer, int which, int kv_head, int64_t t0, int64_t t1, unsigned short *dst,
                           hipStream_t st);
 
 // ---- teacher-forced evaluation helpers (models/modeling_live.py:29-42, 44-168, 170-171)
@@ -77,8 +88,8 @@ hipError_t read_kv_launch(KvGeom kv, int layer, int which, int kv_head, int64_t 
 hipError_t joint_embed_launch(const unsigned short *table, const int64_t *ids, int k, int64_t v_id, const unsigned short *frame_rows,
                               int n_frame_rows, int H, int64_t vocab, int *src_idx_scratch, int *count_out, unsigned short *out,
                               hipStream_t st);
-// copy `pages` whole KV pages (all layers, K and V^T) from the physical pages src_pt[i] to dst_pt[i] (device int arrays)
-hipError_t kv_copy_pages_launch(KvGeom kv, const int *src_pt, const int *dst_pt, int pages, int layers, hipStream_t st);
+// copy `pages` whole KV pages (all layers, K and V^T) from the physical pages src_pt[i] to dst_pt[i] (device int arrays); the page's BYTES
+hipError_t kv_copy_pages_launch(const KvPool &kv, const int *src_pt, const int *dst_pt, int pages, int layers, hipStream_t st);
 // per-row logit statistics, see llm_ops.hip
 hipError_t logit_rows_launch(const unsigned short *logits, int n, int V, int64_t ld, const int64_t *labels, int interval_id, float *lse,
                              int64_t *amax, float *label_logit, float *p_interval, int64_t *p_amax, hipStream_t st);

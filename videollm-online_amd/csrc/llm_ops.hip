@@ -59,7 +59,31 @@ __global__ __launch_bounds__(512) void attn_chunk_kernel(const bf16_t *__restric
 #define VLO_ATTN_BZ blockIdx.z
 #define VLO_ATTN_GX gridDim.x
 #define VLO_ATTN_EXIT return
+#define VLO_ATTN_F8 0
 #include "attn_body.inc"
+#undef VLO_ATTN_F8
+#undef VLO_ATTN_BX
+#undef VLO_ATTN_BY
+#undef VLO_ATTN_BZ
+#undef VLO_ATTN_GX
+#undef VLO_ATTN_EXIT
+}
+// the same over an fp8 e4m3 pool (vlo_config.kv_dtype = 1): kv_scale = the pool's [layer][2] {k_scale, v_scale}
+template <int HD, int HPW>
+__global__ __launch_bounds__(512) void attn_chunk_f8_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int KS,
+                                                            int64_t pos0, int n, int chunk, float scale,
+                                                            float *__restrict__ part_o, float *__restrict__ part_ml, const float *__restrict__ kv_scale) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
+    scale *= kv_scale[2 * layer];                                          // (q . k_code) k_scale / sqrt(d)
+    const float vscale = kv_scale[2 * layer + 1];
+#define VLO_ATTN_BX blockIdx.x
+#define VLO_ATTN_BY blockIdx.y
+#define VLO_ATTN_BZ blockIdx.z
+#define VLO_ATTN_GX gridDim.x
+#define VLO_ATTN_EXIT return
+#define VLO_ATTN_F8 1
+#include "attn_body.inc"
+#undef VLO_ATTN_F8
 #undef VLO_ATTN_BX
 #undef VLO_ATTN_BY
 #undef VLO_ATTN_BZ
@@ -80,171 +104,20 @@ __global__ __launch_bounds__(512) void attn_chunk_kernel(const bf16_t *__restric
 template <int HD, int NCT>
 __global__ __launch_bounds__(512) void attn_cols_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int64_t pos0, int n,
                                                         int chunk, float scale, float *__restrict__ part_o, float *__restrict__ part_ml) {
-    constexpr int NKK = HD / 32, NDT = HD / 16, KS = 8;
-    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];         // the block's one dynamic LDS array (shared name with attn_chunk_kernel)
-    uint4 *qs = reinterpret_cast<uint4 *>(lds_o);                          // [NCT][NKK][64]   Q fragments (MFMA B operand)
-    float4 *lds_po = lds_o + NCT * NKK * 64;                               // [4][NCT][NDT][64] partial O of the merge rounds
-    float *lds_ml = reinterpret_cast<float *>(lds_po + 4 * NCT * NDT * 64); // [4][NCT][16][2]
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int split = blockIdx.x, kvh = blockIdx.y;
-    const int col = lane & 15, qd = lane >> 4;
-    const int L = (int)(pos0 + n);
-    const int c0 = split * chunk, c1 = min(L, c0 + chunk);
-
-    for (int i = w; i < NCT * NKK; i += KS) {
-        const int ct = i / NKK, kk = i - ct * NKK;
-        const int cc = ct * 16 + col, qi = cc / G, h = cc - qi * G;
-        uint4 z = make_uint4(0, 0, 0, 0);
-        if (qi < n) z = *reinterpret_cast<const uint4 *>(q + (size_t)qi * nh * HD + (size_t)(kvh * G + h) * HD + kk * 32 + qd * 8);
-        qs[i * 64 + lane] = z;
-    }
-    int qpos[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) qpos[ct] = (int)pos0 + min((ct * 16 + col) / G, n - 1);
-
-    f32x4 O[NCT][NDT];
-    float mrun[NCT], lrun[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-        mrun[ct] = -INFINITY;
-        lrun[ct] = 0.f;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) O[ct][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    const bf16_t *kbase = kv.k_pool + (size_t)layer * kv.layer_stride;
-    const bf16_t *vbase = kv.vt_pool + (size_t)layer * kv.layer_stride;
-    const int krow = (col >> 2) * 8 + (col & 3);                           // S row `col` of tile t is key krow + 4 t of the block
-    auto load_k = [&](int kt0, frag_ab (&dst)[2][NKK]) {
-        const int page = kv.page_table[kt0 / VLO_PAGE_TOKENS];
-        const bf16_t *kp = kbase + (size_t)page * kv.page_elems + ((size_t)kvh * VLO_PAGE_TOKENS + kt0 % VLO_PAGE_TOKENS) * HD;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk)
-                dst[t][kk] = *reinterpret_cast<const frag_ab *>(kp + (size_t)(krow + 4 * t) * HD + kk * 32 + qd * 8);
-    };
-    frag_ab kf[2][NKK], kn[2][NKK];
-    const int kfirst = c0 + w * 32;
-    if (kfirst < c1) load_k(kfirst, kf);
-    __syncthreads();                                                        // Q fragments staged
-    for (int kt0 = kfirst; kt0 < c1; kt0 += KS * 32) {
-        const int page = kv.page_table[kt0 / VLO_PAGE_TOKENS];
-        const bf16_t *vp = vbase + (size_t)page * kv.page_elems + ((size_t)kvh * HD) * VLO_PAGE_TOKENS + kt0 % VLO_PAGE_TOKENS;
-        frag_ab vf[NDT];
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) vf[dt] = *reinterpret_cast<const frag_ab *>(vp + (size_t)(dt * 16 + col) * VLO_PAGE_TOKENS + qd * 8);
-        const bool more = kt0 + KS * 32 < c1;
-        if (more) load_k(kt0 + KS * 32, kn);
-        asm volatile("" ::: "memory");                                     // the Q fragments are re-read from LDS every block, never hoisted into registers
-        const int kb = kt0 + qd * 8;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const frag_ab qf = __builtin_bit_cast(frag_ab, qs[(ct * NKK + kk) * 64 + lane]);
-                s0 = mfma_bf16(kf[0][kk], qf, s0);
-                s1 = mfma_bf16(kf[1][kk], qf, s1);
-            }
-            float v[8];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                v[r] = (kb + r <= qpos[ct]) ? s0[r] * scale : -INFINITY;
-                v[4 + r] = (kb + 4 + r <= qpos[ct]) ? s1[r] * scale : -INFINITY;
-            }
-            float tmax = v[0];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) tmax = fmaxf(tmax, v[j]);
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float m_new = fmaxf(mrun[ct], tmax);
-            const float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = __expf(mrun[ct] - m_safe);
-            mrun[ct] = m_new;
-            float psum = 0.f;
-            float p[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                p[j] = __expf(v[j] - m_safe);
-                psum += p[j];
-            }
-            const uint4 pk = make_uint4(pack2bf(p[0], p[1]), pack2bf(p[2], p[3]), pack2bf(p[4], p[5]), pack2bf(p[6], p[7]));
-            const frag_ab pb = __builtin_bit_cast(frag_ab, pk);
-            lrun[ct] = lrun[ct] * alpha + psum;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                f32x4 o = O[ct][dt];
-                o[0] *= alpha; o[1] *= alpha; o[2] *= alpha; o[3] *= alpha;
-                O[ct][dt] = mfma_bf16(vf[dt], pb, o);
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int kk = 0; kk < NKK; ++kk) kf[t][kk] = kn[t][kk];
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-        lrun[ct] += __shfl_xor(lrun[ct], 16, 64);
-        lrun[ct] += __shfl_xor(lrun[ct], 32, 64);
-    }
-    // ---- pairwise merge of the 8 partial states: wave w + half hands its state to wave w
-    for (int half = KS / 2; half >= 1; half >>= 1) {
-        if (w >= half && w < 2 * half) {
-            const int slot = w - half;
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                if (qd == 0) {
-                    lds_ml[((slot * NCT + ct) * 16 + col) * 2] = mrun[ct];
-                    lds_ml[((slot * NCT + ct) * 16 + col) * 2 + 1] = lrun[ct];
-                }
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) {
-                    const f32x4 o = O[ct][dt];
-                    lds_po[((size_t)(slot * NCT + ct) * NDT + dt) * 64 + lane] = make_float4(o[0], o[1], o[2], o[3]);
-                }
-            }
-        }
-        __syncthreads();
-        if (w < half) {
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                const float mo = lds_ml[((w * NCT + ct) * 16 + col) * 2], lo = lds_ml[((w * NCT + ct) * 16 + col) * 2 + 1];
-                const float M = fmaxf(mrun[ct], mo);
-                const float Ms = (M == -INFINITY) ? 0.f : M;
-                const float wa = __expf(mrun[ct] - Ms), wb = __expf(mo - Ms);          // -inf -> 0
-                lrun[ct] = lrun[ct] * wa + lo * wb;
-                mrun[ct] = M;
-#pragma unroll
-                for (int dt = 0; dt < NDT; ++dt) {
-                    const float4 o = lds_po[((size_t)(w * NCT + ct) * NDT + dt) * 64 + lane];
-                    O[ct][dt][0] = O[ct][dt][0] * wa + o.x * wb;
-                    O[ct][dt][1] = O[ct][dt][1] * wa + o.y * wb;
-                    O[ct][dt][2] = O[ct][dt][2] * wa + o.z * wb;
-                    O[ct][dt][3] = O[ct][dt][3] * wa + o.w * wb;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (w != 0) return;
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-        const int cc = ct * 16 + col, qi = cc / G, h = cc - qi * G;
-        if (qi >= n) continue;
-        const size_t row = ((size_t)split * nh + kvh * G + h) * 16 + qi;
-        if (qd == 0) {
-            part_ml[row * 2] = mrun[ct];
-            part_ml[row * 2 + 1] = lrun[ct];
-        }
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt) {
-            const f32x4 o = O[ct][dt];
-            *reinterpret_cast<float4 *>(part_o + row * HD + dt * 16 + qd * 4) = make_float4(o[0], o[1], o[2], o[3]);
-        }
-    }
+#define VLO_ATTN_F8 0
+#include "attn_cols_body.inc"
+#undef VLO_ATTN_F8
+}
+// the same over an fp8 e4m3 pool (vlo_config.kv_dtype = 1): kv_scale = the pool's [layer][2] {k_scale, v_scale}
+template <int HD, int NCT>
+__global__ __launch_bounds__(512) void attn_cols_f8_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int64_t pos0, int n,
+                                                           int chunk, float scale, float *__restrict__ part_o, float *__restrict__ part_ml,
+                                                           const float *__restrict__ kv_scale) {
+    scale *= kv_scale[2 * layer];                                          // (q . k_code) k_scale / sqrt(d)
+    const float vscale = kv_scale[2 * layer + 1];
+#define VLO_ATTN_F8 1
+#include "attn_cols_body.inc"
+#undef VLO_ATTN_F8
 }
 
 // Merge of the split-KV partials.  grid = (nh, n); block = 256 threads = SL split-lanes x CL column-lanes of 4 columns (HD = 128:
@@ -367,12 +240,14 @@ __global__ __launch_bounds__(512, 4) void attn_prefill_pp_kernel(const bf16_t *_
 }
 // the (head dim, GQA group) pairs attn_prefill_kernel is instantiated for — attention_prefill_launch returns hipErrorNotSupported for any other; a caller
 // WITHOUT a fallback (tp.hip::tp_prefill) asks first and keeps the 16-row step instead
-bool attention_prefill_supported(int head_dim, int gqa_group) {
+bool attention_prefill_supported(int head_dim, int gqa_group, int kv_dtype) {
+    if (kv_dtype != VLO_KV_BF16) return false;
     return (head_dim == 128 && (gqa_group == 1 || gqa_group == 2 || gqa_group == 4 || gqa_group == 8)) ||
            (head_dim == 64 && (gqa_group == 2 || gqa_group == 4 || gqa_group == 8));
 }
 
-hipError_t attention_prefill_launch(const unsigned short *q, KvGeom kv, int layer, int num_heads, int64_t pos0, int n, unsigned short *out, hipStream_t st) {
+hipError_t attention_prefill_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n, unsigned short *out, hipStream_t st) {
+    if (kv.dtype != VLO_KV_BF16) return hipErrorNotSupported;             // the flash kernels read bf16 pages: the caller takes attention_launch
     const int nkv = kv.num_kv_heads, hd = kv.head_dim, G = num_heads / nkv;
     if (n <= 0 || nkv * G != num_heads) return hipErrorInvalidValue;
     const float scale = (1.0f / sqrtf((float)hd)) * 1.4426950408889634f;   // log2(e) / sqrt(hd): the kernels' softmax runs on exp2 (attn_prefill_pp_body.inc)
@@ -439,7 +314,7 @@ hipError_t attention_geometry(const KvGeom &kv, int num_heads, int64_t pos0, int
     return hipSuccess;
 }
 
-hipError_t attention_launch(const unsigned short *q, KvGeom kv, int layer, int num_heads, int64_t pos0, int n,
+hipError_t attention_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n,
                             float *part_o, float *part_ml, unsigned short *out, hipStream_t st, int pack_row0, int part_cap) {
     AttnGeom ag;
     const hipError_t ge = attention_geometry(kv, num_heads, pos0, n, &ag, part_cap);
@@ -461,11 +336,29 @@ hipError_t attention_launch(const unsigned short *q, KvGeom kv, int layer, int n
         (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipGetLastError();
         attr_done = true;
     }
-#define VLO_ATTN_COLS(HD_, NCT_) \
-    hipLaunchKernelGGL((attn_cols_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kv, layer, num_heads, G, pos0, n, chunk, scale, part_o, part_ml)
+    const KvGeom &kg = kv;
+    const bool f8 = kv.dtype == VLO_KV_FP8;
+    if (f8 && !kv.scale) return hipErrorInvalidValue;
+#define VLO_ATTN_COLS(HD_, NCT_)                                                                                                                 \
+    do {                                                                                                                                         \
+        if (f8) hipLaunchKernelGGL((attn_cols_f8_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale, \
+                                   part_o, part_ml, kv.scale);                                                                                   \
+        else hipLaunchKernelGGL((attn_cols_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale,      \
+                                part_o, part_ml);                                                                                                \
+    } while (0)
     if (ag.nct) {
         if (hd == 128 && ag.nct == 1) VLO_ATTN_COLS(128, 1);
         else if (hd == 128 && ag.nct == 2) VLO_ATTN_COLS(128, 2);
@@ -478,8 +371,13 @@ hipError_t attention_launch(const unsigned short *q, KvGeom kv, int layer, int n
         return attn_combine_launch(part_o, part_ml, nsplit, num_heads, hd, n, out, pack_row0, st);
     }
 #undef VLO_ATTN_COLS
-#define VLO_ATTN(HD_, HPW_) \
-    hipLaunchKernelGGL((attn_chunk_kernel<HD_, HPW_>), grid, block, lds, st, q, kv, layer, num_heads, G, KS, pos0, n, chunk, scale, part_o, part_ml)
+#define VLO_ATTN(HD_, HPW_)                                                                                                                      \
+    do {                                                                                                                                         \
+        if (f8) hipLaunchKernelGGL((attn_chunk_f8_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk,      \
+                                   scale, part_o, part_ml, kv.scale);                                                                            \
+        else hipLaunchKernelGGL((attn_chunk_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk, scale,     \
+                                part_o, part_ml);                                                                                                \
+    } while (0)
     if (hd == 128 && hpw == 2) VLO_ATTN(128, 2);
     else if (hd == 128 && hpw == 1) VLO_ATTN(128, 1);
     else if (hd == 64 && hpw == 2) VLO_ATTN(64, 2);
@@ -556,10 +454,33 @@ __global__ void read_kv_kernel(KvGeom kv, int layer, int which, int kvh, int64_t
         dst[(size_t)blockIdx.x * hd + d] = v;
     }
 }
-hipError_t read_kv_launch(KvGeom kv, int layer, int which, int kv_head, int64_t t0, int64_t t1, unsigned short *dst,
+// fp8 pool: bf16(code * scale) — the value attention multiplies with (exact when the scale is a power of two)
+__global__ void read_kv_f8_kernel(KvGeom kv, int layer, int which, int kvh, int64_t t0, const float *__restrict__ kv_scale, bf16_t *__restrict__ dst) {
+    const int64_t t = t0 + blockIdx.x;
+    const int page = kv.page_table[t / VLO_PAGE_TOKENS];
+    const int tok = (int)(t % VLO_PAGE_TOKENS);
+    const int hd = kv.head_dim;
+    const float sc = kv_scale[2 * layer + which];
+    const uint8_t *k8 = reinterpret_cast<const uint8_t *>(kv.k_pool), *v8 = reinterpret_cast<const uint8_t *>(kv.vt_pool);
+    for (int d = threadIdx.x; d < hd; d += blockDim.x) {
+        uint8_t c;
+        if (which == 0)
+            c = k8[(size_t)layer * kv.layer_stride + (size_t)page * kv.page_elems + ((size_t)kvh * VLO_PAGE_TOKENS + tok) * hd + d];
+        else
+            c = v8[(size_t)layer * kv.layer_stride + (size_t)page * kv.page_elems + ((size_t)kvh * hd + d) * VLO_PAGE_TOKENS + tok];
+        dst[(size_t)blockIdx.x * hd + d] = f2bf(fp8_to_f32(c) * sc);
+    }
+}
+hipError_t read_kv_launch(const KvPool &kv, int layer, int which, int kv_head, int64_t t0, int64_t t1, unsigned short *dst,
                           hipStream_t st) {
     if (t1 <= t0) return hipSuccess;
-    hipLaunchKernelGGL(read_kv_kernel, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, kv, layer, which, kv_head, t0, dst);
+    const KvGeom &kg = kv;
+    if (kv.dtype == VLO_KV_FP8) {
+        if (!kv.scale) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(read_kv_f8_kernel, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, kg, layer, which, kv_head, t0, kv.scale, dst);
+    } else {
+        hipLaunchKernelGGL(read_kv_kernel, dim3((unsigned)(t1 - t0)), dim3(64), 0, st, kg, layer, which, kv_head, t0, dst);
+    }
     return hipGetLastError();
 }
 
@@ -761,9 +682,16 @@ __global__ void kv_copy_pages_kernel(KvGeom kv, const int *__restrict__ src_pt, 
     const int n16 = (int)(kv.page_elems / 8);
     for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
 }
-hipError_t kv_copy_pages_launch(KvGeom kv, const int *src_pt, const int *dst_pt, int pages, int layers, hipStream_t st) {
+hipError_t kv_copy_pages_launch(const KvPool &kv, const int *src_pt, const int *dst_pt, int pages, int layers, hipStream_t st) {
     if (pages <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kv_copy_pages_kernel, dim3(pages, layers, 2), dim3(256), 0, st, kv, src_pt, dst_pt);
+    KvGeom g = kv;
+    if (kv.dtype == VLO_KV_FP8) {
+        // the kernel moves 16-bit elements: an e4m3 page of page_elems bytes is page_elems / 2 of them, its strides likewise (page_elems is a
+        // multiple of VLO_PAGE_TOKENS * 64, so the halves stay whole 16-byte vectors)
+        g.layer_stride /= 2;
+        g.page_elems /= 2;
+    }
+    hipLaunchKernelGGL(kv_copy_pages_kernel, dim3(pages, layers, 2), dim3(256), 0, st, g, src_pt, dst_pt);
     return hipGetLastError();
 }
 

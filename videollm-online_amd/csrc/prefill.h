@@ -11,7 +11,8 @@ int gemm64_plan(int K, Gemm64Plan *p, bool even_kf = false);     // even_kf: the
 // y[m][n] = sum_k x[m][k] W[n][k] for up to 64 rows of x against the SAME packed weight image the 16-row GEMV streams
 // (gemv.hip; bf16, or fp8 e4m3 + scales when a.wq); epilogues EPI_BF16 / EPI_SWIGLU / EPI_RESID / EPI_ROPE with the rounding points of the GEMV path.
 // x is a PACKED-64 matrix (llm_ops.h::vlo_pack64_elem); EPI_SWIGLU also writes its output packed-64 (it feeds the down
-// projection).  Uses of GemvArgs: Wp, x, K, NT, N_valid, n_rows (<= 64), out_bf16 (+ ldo), h + ldo, cos/sin/kv/layer/num_heads/pos0.
+// projection).  Uses of GemvArgs: Wp, x, K, NT, N_valid, n_rows (<= 64), out_bf16 (+ ldo), h + ldo, cos/sin/kv/layer/num_heads/pos0 (+ kv_scale:
+// EPI_ROPE_F8).
 hipError_t gemm64_launch(GemvArgs a, const Gemm64Plan &p, int epi, hipStream_t st);
 
 // ---- long inputs (teacher-forced evaluation, first step of a long prompt): blocks of up to VLO_PREFILL_TOKENS tokens ------------------
@@ -48,6 +49,6 @@ bool llm_gemm_fp8_ok(int N, int K);
 hipError_t llm_gemm_fp8_launch(const void *Xq, const float *xscale, const void *Wp8, const float *wscale, int M, int N, int K, void *out, int ldo,
                                int kind, hipStream_t st);
 // qkv bf16 [M][(nh + 2 nkv) hd] (projection outputs) -> RoPE (HF rounding points) -> q bf16 [M][nh hd], K / V^T appended to the paged pool
-// at positions pos0 .. pos0 + M - 1
+// at positions pos0 .. pos0 + M - 1 (an fp8 pool: quantised with the layer's scales, llm_ops.h KvPool)
 hipError_t rope_kv_append_launch(const unsigned short *qkv, int M, int num_heads, const unsigned short *cos_tab, const unsigned short *sin_tab,
-                                 KvGeom kv, int layer, long long pos0, unsigned short *q_out, hipStream_t st);
+                                 const KvPool &kv, int layer, long long pos0, unsigned short *q_out, hipStream_t st);

@@ -40,12 +40,12 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
     const int mt_live = (a.n_rows + 15) >> 4;                              // token tiles that hold real rows
 
     const int hd = a.kv.head_dim;
-    const int tph = (EPI == EPI_ROPE) ? hd / 16 : 2;
+    const int tph = epi_rope(EPI) ? hd / 16 : 2;
     const int hp = tph / 2;
-    const bool single = (EPI != EPI_ROPE && a.CT == 1);
-    const int ngroups = (EPI == EPI_ROPE) ? a.NT / 2 : (single ? a.NT : (a.NT + 1) / 2);
-    auto tile_a = [&](int g) { return (EPI == EPI_ROPE) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
-    auto tile_b = [&](int g) { return (EPI == EPI_ROPE) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
+    const bool single = (!epi_rope(EPI) && a.CT == 1);
+    const int ngroups = epi_rope(EPI) ? a.NT / 2 : (single ? a.NT : (a.NT + 1) / 2);
+    auto tile_a = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
+    auto tile_b = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
 
     const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ ? kfw0 / 2 : kfw0) * 64 + lane;
     const size_t tile_stride = (size_t)(WQ ? KFtot / 2 : KFtot) * 64;
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
             }
             return s;
         };
-        if (EPI == EPI_ROPE) {
+        if (epi_rope(EPI)) {
             // a lane needs both tiles of the rotary pair: items = (token tile, lane)
             for (int t = threadIdx.x; t < MT * 64; t += blockDim.x) {
                 const int mt = t >> 6, l = t & 63;
@@ -164,8 +164,27 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
                         lo[r] = f2bf(rbf(x1 * cs) + rbf(-x2 * sn));                // q*cos + rotate_half(q)*sin, bf16 at every op
                         hi[r] = f2bf(rbf(x2 * cs) + rbf(x1 * sn));
                     }
-                    *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
-                    *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
+                    if (EPI == EPI_ROPE_F8 && head >= nh) {                 // fp8 pool (gemv_epi.inc): K row quantised with k_scale
+                        const float ks = a.kv_scale[2 * a.layer];
+                        uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.k_pool) + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
+                                      ((size_t)(head - nh) * VLO_PAGE_TOKENS + tok) * hd;
+                        *reinterpret_cast<unsigned *>(d8 + i) = fp8x4_quant(bf2f(lo[0]), bf2f(lo[1]), bf2f(lo[2]), bf2f(lo[3]), ks);
+                        *reinterpret_cast<unsigned *>(d8 + half + i) = fp8x4_quant(bf2f(hi[0]), bf2f(hi[1]), bf2f(hi[2]), bf2f(hi[3]), ks);
+                    } else {
+                        *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
+                        *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
+                    }
+                } else if (EPI == EPI_ROPE_F8) {                            // fp8 V^T: byte stores, 16 consecutive tokens per row of the wave
+                    const float vs = a.kv_scale[2 * a.layer + 1];
+                    uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.vt_pool) + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
+                                  ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;
+                    const unsigned ca = fp8x4_quant(rbf(va[0]), rbf(va[1]), rbf(va[2]), rbf(va[3]), vs);
+                    const unsigned cb = fp8x4_quant(rbf(vb[0]), rbf(vb[1]), rbf(vb[2]), rbf(vb[3]), vs);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        d8[(size_t)(i + r) * VLO_PAGE_TOKENS] = (uint8_t)(ca >> (8 * r));
+                        d8[(size_t)(half + i + r) * VLO_PAGE_TOKENS] = (uint8_t)(cb >> (8 * r));
+                    }
                 } else {
                     bf16_t *dst = a.kv.vt_pool + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
                                   ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;
@@ -247,6 +266,7 @@ static hipError_t launch64(const GemvArgs &a, int epi, dim3 grid, dim3 block, si
         return hipGetLastError();                                                         \
     } while (0)
     if (epi == EPI_ROPE) VLO_GO64(EPI_ROPE);
+    if (epi == EPI_ROPE_F8) VLO_GO64(EPI_ROPE_F8);
     if (epi == EPI_SWIGLU) VLO_GO64(EPI_SWIGLU);
     if (epi == EPI_RESID) VLO_GO64(EPI_RESID);
     if (epi == EPI_BF16) VLO_GO64(EPI_BF16);
@@ -256,11 +276,12 @@ static hipError_t launch64(const GemvArgs &a, int epi, dim3 grid, dim3 block, si
 
 hipError_t gemm64_launch(GemvArgs a, const Gemm64Plan &p, int epi, hipStream_t st) {
     if (a.n_rows <= 0 || a.n_rows > VLO_BLOCK_TOKENS) return hipErrorInvalidValue;
-    if (epi == EPI_ROPE && ((a.NT & 1) || (a.kv.head_dim != 64 && a.kv.head_dim != 128))) return hipErrorInvalidValue;
+    if (epi == EPI_ROPE_F8 && !a.kv_scale) return hipErrorInvalidValue;
+    if (epi_rope(epi) && ((a.NT & 1) || (a.kv.head_dim != 64 && a.kv.head_dim != 128))) return hipErrorInvalidValue;
     a.KC = p.KC;
     // single column tiles when pairs would leave most CUs without work (o_proj / down_proj: 256 tiles)
-    a.CT = (epi != EPI_ROPE && (a.NT + 1) / 2 < 256) ? 1 : 2;
-    const int ngroups = (epi == EPI_ROPE) ? a.NT / 2 : (a.CT == 1 ? a.NT : (a.NT + 1) / 2);
+    a.CT = (!epi_rope(epi) && (a.NT + 1) / 2 < 256) ? 1 : 2;
+    const int ngroups = epi_rope(epi) ? a.NT / 2 : (a.CT == 1 ? a.NT : (a.NT + 1) / 2);
     int gx = ngroups < 256 ? ngroups : 256;                                // one resident 8-wave block per CU
     const int per = (ngroups + gx - 1) / gx;
     gx = (ngroups + per - 1) / per;
@@ -454,11 +475,69 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(const bf16_t *__res
     }
 }
 
+// the same appending to an fp8 e4m3 pool: K after RoPE quantised with kv_scale[2 layer], V with kv_scale[2 layer + 1] (the bf16 values the bf16
+// kernel stores, gemv_epi.inc's rule); a thread's 4 + 4 V^T bytes are VLO_PAGE_TOKENS apart
+__global__ __launch_bounds__(256) void rope_kv_append_f8_kernel(const bf16_t *__restrict__ qkv, int M, int nh, const bf16_t *__restrict__ cos_tab,
+                                                                const bf16_t *__restrict__ sin_tab, KvGeom kv, int layer, long long pos0,
+                                                                bf16_t *__restrict__ q_out, const float *__restrict__ kv_scale) {
+    const int hd = kv.head_dim, half = hd >> 1, nkv = kv.num_kv_heads, heads = nh + 2 * nkv, per_head = half >> 2;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)M * heads * per_head) return;
+    const int i = (int)(idx % per_head) * 4, head = (int)((idx / per_head) % heads), m = (int)(idx / ((long long)per_head * heads));
+    const bf16_t *src = qkv + (size_t)m * heads * hd + (size_t)head * hd;
+    const ushort4 a4 = *reinterpret_cast<const ushort4 *>(src + i), b4 = *reinterpret_cast<const ushort4 *>(src + half + i);
+    const bf16_t va[4] = {a4.x, a4.y, a4.z, a4.w}, vb[4] = {b4.x, b4.y, b4.z, b4.w};
+    const long long pos = pos0 + m;
+    const int page = kv.page_table[pos / VLO_PAGE_TOKENS], tok = (int)(pos % VLO_PAGE_TOKENS);
+    const size_t lp = (size_t)layer * kv.layer_stride + (size_t)page * kv.page_elems;
+    if (head < nh + nkv) {
+        const ushort4 c4 = *reinterpret_cast<const ushort4 *>(cos_tab + pos * half + i), s4 = *reinterpret_cast<const ushort4 *>(sin_tab + pos * half + i);
+        const bf16_t cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+        float lo[4], hi[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float x1 = bf2f(va[r]), x2 = bf2f(vb[r]), c = bf2f(cc[r]), sn = bf2f(ss[r]);
+            lo[r] = rbf(rbf(x1 * c) + rbf(-x2 * sn));             // HF :157-158, bf16 at every op (rope_kv_append_kernel)
+            hi[r] = rbf(rbf(x2 * c) + rbf(x1 * sn));
+        }
+        if (head < nh) {
+            bf16_t *dst = q_out + (size_t)m * nh * hd + (size_t)head * hd;
+            ushort4 o;
+            o.x = f2bf(lo[0]); o.y = f2bf(lo[1]); o.z = f2bf(lo[2]); o.w = f2bf(lo[3]);
+            *reinterpret_cast<ushort4 *>(dst + i) = o;
+            o.x = f2bf(hi[0]); o.y = f2bf(hi[1]); o.z = f2bf(hi[2]); o.w = f2bf(hi[3]);
+            *reinterpret_cast<ushort4 *>(dst + half + i) = o;
+        } else {
+            const float ks = kv_scale[2 * layer];
+            uint8_t *d8 = reinterpret_cast<uint8_t *>(kv.k_pool) + lp + ((size_t)(head - nh) * VLO_PAGE_TOKENS + tok) * hd;
+            *reinterpret_cast<unsigned *>(d8 + i) = fp8x4_quant(lo[0], lo[1], lo[2], lo[3], ks);
+            *reinterpret_cast<unsigned *>(d8 + half + i) = fp8x4_quant(hi[0], hi[1], hi[2], hi[3], ks);
+        }
+    } else {
+        const float vs = kv_scale[2 * layer + 1];
+        uint8_t *d8 = reinterpret_cast<uint8_t *>(kv.vt_pool) + lp + ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;
+        const unsigned ca = fp8x4_quant(bf2f(va[0]), bf2f(va[1]), bf2f(va[2]), bf2f(va[3]), vs);
+        const unsigned cb = fp8x4_quant(bf2f(vb[0]), bf2f(vb[1]), bf2f(vb[2]), bf2f(vb[3]), vs);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            d8[(size_t)(i + r) * VLO_PAGE_TOKENS] = (uint8_t)(ca >> (8 * r));
+            d8[(size_t)(half + i + r) * VLO_PAGE_TOKENS] = (uint8_t)(cb >> (8 * r));
+        }
+    }
+}
+
 hipError_t rope_kv_append_launch(const unsigned short *qkv, int M, int num_heads, const unsigned short *cos_tab, const unsigned short *sin_tab,
-                                 KvGeom kv, int layer, long long pos0, unsigned short *q_out, hipStream_t st) {
+                                 const KvPool &kv, int layer, long long pos0, unsigned short *q_out, hipStream_t st) {
     if (M <= 0 || (kv.head_dim & 7)) return hipErrorInvalidValue;
     const long long total = (long long)M * (num_heads + 2 * kv.num_kv_heads) * (kv.head_dim >> 3);
-    hipLaunchKernelGGL(rope_kv_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, qkv, M, num_heads, cos_tab, sin_tab, kv, layer,
-                       pos0, q_out);
+    const KvGeom &kg = kv;
+    if (kv.dtype == VLO_KV_FP8) {
+        if (!kv.scale) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(rope_kv_append_f8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, qkv, M, num_heads, cos_tab, sin_tab, kg,
+                           layer, pos0, q_out, kv.scale);
+    } else {
+        hipLaunchKernelGGL(rope_kv_append_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, qkv, M, num_heads, cos_tab, sin_tab, kg,
+                           layer, pos0, q_out);
+    }
     return hipGetLastError();
 }

@@ -654,13 +654,14 @@ static int tp_chunk(vlo_tp_session *t, const unsigned short *src, int m, bool wa
             vlo_session *s = t->ss[r];
             vlo_engine *e = s->e;
             const LayerWeights &L = e->layers[l];
-            const KvGeom kv = kv_geom(s);
+            const KvPool kv = kv_geom(s);
             if (l == 0)                         // later layers: x comes out of the reduce + norm that closed the previous layer
                 TP_TRY(add_rmsnorm_launch(s->h, nullptr, 0, H, (const unsigned short *)L.ln_in, s->x, H, H, c.rms_eps, m, st));
             GemvArgs a = gemv_args(L.qkv, s->x, H, m);
             a.out_bf16 = s->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.kv = kv; a.layer = l; a.num_heads = e->nh_l; a.pos0 = s->len;
-            TP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, EPI_ROPE, st));
+            a.layer = l; a.num_heads = e->nh_l; a.pos0 = s->len;
+            const int epi = rope_epi(a, kv);
+            TP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
             TP_TRY(attention_launch(s->q, kv, l, e->nh_l, s->len, m, s->part_o, s->part_ml, s->attn, st));
             GemvArgs o = gemv_args(L.o, s->attn, e->nh_l * hd, m);
             if (r == 0 && (pub_o = p2p_direct(g, L.o.plan))) xo = p2p_begin_reduce(g);
@@ -730,9 +731,9 @@ static bool tp_prefill_ok(const vlo_tp_session *t) {
     const vlo_tp_group *g = t->g;
     if (!(g->comm || (int)g->eng.size() == g->tp_size)) return false;       // mailbox-only groups keep the 16-row step
     // tp_prefill has no fallback for its attention launch (the one-GPU run_prefill has: attention_launch over pooled partials), so a shard shape the
-    // flash kernel is not built for — hd 64 MHA, G = 16, odd groups — keeps the 16-row step for long inputs
+    // flash kernel is not built for — hd 64 MHA, G = 16, odd groups, an fp8 KV pool — keeps the 16-row step for long inputs
     for (const vlo_engine *e : g->eng)
-        if (!prefill_ok(e) || e->nkv_l <= 0 || e->nh_l % e->nkv_l || !attention_prefill_supported(e->head_dim, e->nh_l / e->nkv_l)) return false;
+        if (!prefill_ok(e) || e->nkv_l <= 0 || e->nh_l % e->nkv_l || !attention_prefill_supported(e->head_dim, e->nh_l / e->nkv_l, e->cfg.kv_dtype)) return false;
     return true;
 }
 static int tp_prefill_exchange(vlo_tp_session *t, int m, const void *(*norm_w)(const vlo_engine *, int), int layer, hipStream_t st) {
@@ -777,7 +778,7 @@ static int tp_prefill(vlo_tp_session *t, const unsigned short *src, int m, bool 
             vlo_session *s = t->ss[r];
             vlo_engine *e = s->e;
             const LayerWeights &L = e->layers[l];
-            const KvGeom kv = kv_geom(s);
+            const KvPool kv = kv_geom(s);
             const int qd = e->nh_l * hd, Nqkv = qd + 2 * e->nkv_l * hd;
             if (l == 0) TP_TRY(add_rmsnorm_launch(s->ph, nullptr, 0, H, (const unsigned short *)L.ln_in, s->px, H, H, c.rms_eps, m, st));
             if ((rc = prefill_gemm(s, s->px, L.qkv, m, Nqkv, H, s->pqkv, Nqkv, LLM_GEMM_BF16, st))) return rc;

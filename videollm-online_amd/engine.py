@@ -8,6 +8,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _C
+from .checkpoint import is_kv_scale
 
 _DT = {torch.float32: _C.DT_F32, torch.bfloat16: _C.DT_BF16, torch.float16: _C.DT_F16}
 
@@ -39,6 +40,10 @@ class EngineConfig:
     # fp8 engines only: "fp8" = the long-input (prefill) projections quantise their X rows to e4m3 (one fp32 scale per row) and run on the native
     # fp8 MFMA (include/vlo.h vlo_config.prefill_act_dtype); "bf16" = expand the weight image per GEMM, bf16 MFMA.  The live step is bf16 either way.
     prefill_act_dtype: str = "bf16"
+    # storage of the paged KV cache: "bf16", or "fp8" = one OCP e4m3 byte per element with static per-layer k_scale / v_scale (include/vlo.h
+    # vlo_config.kv_dtype; weights "model.layers.{i}.self_attn.k_scale" / "v_scale", 1.0 when absent).  Half the KV bytes per token; composes
+    # with weight_dtype and prefill_act_dtype
+    kv_dtype: str = "bf16"
 
     def to_c(self) -> _C.VloConfig:
         c = _C.VloConfig()
@@ -56,6 +61,9 @@ class EngineConfig:
         if self.prefill_act_dtype not in ("bf16", "fp8") or (self.prefill_act_dtype == "fp8" and self.weight_dtype != "fp8"):
             raise ValueError("prefill_act_dtype must be 'bf16', or 'fp8' on an engine with weight_dtype='fp8'")
         c.prefill_act_dtype = 1 if self.prefill_act_dtype == "fp8" else 0
+        if self.kv_dtype not in ("bf16", "fp8"):
+            raise ValueError("kv_dtype must be 'bf16' or 'fp8'")
+        c.kv_dtype = 1 if self.kv_dtype == "fp8" else 0
         if self.vit:
             v = self.vit
             c.has_vit = 1
@@ -148,6 +156,8 @@ class Engine:
 
     def load_weight(self, name: str, t: torch.Tensor):
         t = t.detach().contiguous()
+        if is_kv_scale(name):                 # vLLM stores them as 0-d tensors; the C ABI takes one f32 element
+            t = t.float().reshape(1)
         streamed = (name.startswith("model.layers.") and name.endswith(self._STREAMED)) or name == "lm_head.weight"
         if self.cfg.weight_dtype == "fp8" and streamed and t.dtype != torch.float8_e4m3fn:
             from .checkpoint import quantize_fp8_per_channel
