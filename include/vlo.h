@@ -189,6 +189,32 @@ int vlo_stream_sample(vlo_session *s, float threshold, int interval_id, int64_t 
 int vlo_greedy_generate(vlo_session *s, const void *embeds_dev, int m, int eos_token_id,
                         int64_t *out_ids_dev, int max_new, int force_len, int *n_written, void *stream);
 
+/* ---- batched steps: the live steps of SEVERAL sessions of one engine in one weight pass (a step streams the whole weight
+ *      image whatever its row count, so B sessions stepped together pay for it once).  A batch owns the workspace of one such step
+ *      (activations for 64 rows, split-KV partials, logits [max_sessions][vocab], sampler scratch); the sessions stay independent of it
+ *      and of each other, and may be stepped alone, forked or cropped between batched steps.  Not for tensor-parallel engines.
+ *      A batch is not thread-safe; its calls are ordered on the streams they are given (one stream per batch is the intended use). */
+typedef struct vlo_batch vlo_batch;
+int  vlo_batch_create(vlo_engine *e, int max_sessions /* 1..16 */, vlo_batch **out);
+void vlo_batch_destroy(vlo_batch *b);
+/* embeds_dev bf16 [sum n][hidden], session-major: rows of ss[0] first.  Session b appends n_host[b] >= 1 tokens at ITS positions
+ *      len_b .. len_b + n_b - 1.  sum n <= 16 runs the 16-row pipeline (each session's logits and K / V equal vlo_llm_step's bit for bit),
+ *      17..64 the 64-row block path, more is VLO_E_INVALID (split the batch).  The sessions must be distinct, of this batch's engine,
+ *      1 <= B <= max_sessions.  KV pages for every session are taken before anything is launched: when the pool cannot hold them all the
+ *      call fails and no session changes.  Afterwards every session is where vlo_llm_step would leave it (length, logits of its last row).
+ *      last_logits_dev: NULL or bf16 [B][vocab] = each session's last-row logits. */
+int  vlo_batch_step(vlo_batch *b, vlo_session *const *ss, int B, const void *embeds_dev, const int *n_host,
+                    void *last_logits_dev, void *stream);
+/* vlo_stream_sample on each row of the last vlo_batch_step: tok_dev int64 [B], p_interval_dev NULL or f32 [B] */
+int  vlo_batch_stream_sample(vlo_batch *b, float threshold, int interval_id, int64_t *tok_dev, float *p_interval_dev, void *stream);
+/* fast_greedy_generate (models/modeling_live.py:173-182) for B sessions at once: session b is prefixed with its m_host[b] embedding rows
+ *      (embeds_dev session-major as in vlo_batch_step; one batched step when sum m <= 16, else each session's prefix is stepped alone), then
+ *      decodes one token per batched step until its EOS or max_new; a session that has emitted EOS leaves the batch (EOS is not fed).
+ *      out_ids_dev int64 [B][max_new]; n_written_host[b] = ids written for session b.  Session lengths and logits afterwards are what
+ *      vlo_greedy_generate leaves.  Synchronises the stream once per decode step (the tokens are read on the host). */
+int  vlo_batch_greedy_generate(vlo_batch *b, vlo_session *const *ss, int B, const void *embeds_dev, const int *m_host,
+                               int eos_token_id, int64_t *out_ids_dev, int max_new, int *n_written_host, void *stream);
+
 /* ---- introspection for tests / bench ------------------------------------------------ */
 /* copy the session's K or V for (layer, kv_head) tokens [t0,t1) to dst_dev bf16 [t1-t0, head_dim] (kv_dtype = 1: bf16(code * scale)) */
 int vlo_session_read_kv(vlo_session *s, int layer, int which /*0=K,1=V*/, int kv_head, int64_t t0, int64_t t1,

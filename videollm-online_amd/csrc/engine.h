@@ -132,6 +132,39 @@ struct vlo_session {
     float *ppartial = nullptr;                   // TP prefill: this rank's o-proj / down-proj partial sums fp32 [VLO_PREFILL_TOKENS][H] awaiting the all-reduce
 };
 
+// ---- batched steps (vlo_batch_*): the rows of up to VLO_BATCH_MAX sessions in one weight pass ------------------------------------------
+#define VLO_BATCH_MAX 16
+#define VLO_BATCH_SLOTS 4           // ring of per-step table buffers (see vlo_batch)
+// the per-step tables every layer of a batched step reads: the qkv epilogue's row table (EPI_ROPE_ROWS) and the attention segments
+struct BatchTables {
+    RopeRow rows[VLO_BLOCK_TOKENS];
+    AttnSeg segs[VLO_ATTN_SEG_MAX];
+};
+struct vlo_batch {
+    vlo_engine *e = nullptr;
+    int max_sessions = 0;
+    std::vector<void *> owned;
+    // activations of up to 64 rows; the 16-row pipeline uses them row-major, the block path as run_block does (x, attn, act packed-64)
+    unsigned short *h = nullptr, *x = nullptr, *q = nullptr, *attn = nullptr, *act = nullptr;
+    unsigned short *xl = nullptr;                // [16][H]: the normed last row of each session, the lm_head's input
+    unsigned short *emb = nullptr;               // [16][H]: the next step's input rows of the greedy loop
+    float *partial = nullptr, *sq[2] = {nullptr, nullptr};
+    float *part_o = nullptr, *part_ml = nullptr; // split-KV partial states: max_sessions * attention_states_bound(nkv)
+    int part_cap = 0;
+    unsigned short *logits = nullptr;            // [max_sessions][V]: row b = session b of the last step
+    float *sample_scratch = nullptr;             // [max_sessions][VLO_SAMPLE_SCRATCH_FLOATS]
+    int64_t *tok = nullptr;                      // [max_sessions]
+    int64_t *host_tok = nullptr;                 // pinned [VLO_BATCH_MAX]
+    // the tables change every step: slot k is written on the host (pinned stage[k]), copied to tables_dev[k] on the step's stream and read by
+    // its kernels; slot_ev[k], recorded behind the step's last launch, must have completed before the host rewrites stage[k] (the queued copy
+    // of a step still in flight reads it) — with VLO_BATCH_SLOTS slots the host waits only when it runs that many steps ahead
+    BatchTables *stage = nullptr, *tables_dev = nullptr;
+    hipEvent_t slot_ev[VLO_BATCH_SLOTS] = {};
+    bool slot_used[VLO_BATCH_SLOTS] = {};
+    int slot = 0;
+    int last_B = 0;                              // rows of `logits` written by the last vlo_batch_step (0: none)
+};
+
 int dev_alloc(void **p, size_t bytes);
 // helpers shared with tp.hip
 int ensure_pages(vlo_session *s, int64_t new_len, hipStream_t st);

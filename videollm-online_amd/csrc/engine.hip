@@ -1104,6 +1104,334 @@ int vlo_greedy_generate(vlo_session *s, const void *embeds_dev, int m, int eos_t
     return VLO_OK;
 }
 
+// ---- batched steps: the live steps of several sessions in one weight pass ---------------------------------------------------------------
+// A step streams the whole weight image whatever its row count (gemv_plan depends on K only; rows past n_rows are loaded anyway), so the rows
+// of B sessions share it: the qkv epilogue takes each row's position and KV page from a row table (EPI_ROPE_ROWS), attention runs one segment
+// per (session, 16-query sub-chunk) with that session's page table and its solo split geometry (llm_ops.h AttnSeg), the combine writes every
+// segment's rows back in place, and the last row of each session goes through the lm_head and back to the session.
+int vlo_batch_create(vlo_engine *e, int max_sessions, vlo_batch **out) {
+    if (!e || !out) return fail(VLO_E_INVALID, "null argument");
+    if (!e->finalized) return fail(VLO_E_STATE, "engine not finalized");
+    if (e->tp_size > 1) return fail(VLO_E_STATE, "tensor-parallel engine: batched steps are not supported");
+    if (max_sessions < 1 || max_sessions > VLO_BATCH_MAX) return fail(VLO_E_INVALID, "max_sessions must be 1.." + std::to_string(VLO_BATCH_MAX));
+    const vlo_config &c = e->cfg;
+    if (c.vocab_size & 7) return fail(VLO_E_UNSUPPORTED, "batched steps need vocab_size % 8 == 0");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t H = c.hidden_size, I = e->I_l, hd = e->head_dim, qd = (size_t)e->nh_l * hd, V = c.vocab_size, R = VLO_BLOCK_TOKENS;
+    vlo_batch *b = new vlo_batch();
+    b->e = e;
+    b->max_sessions = max_sessions;
+    int ksmax = 1;
+    for (auto &L : e->layers) ksmax = std::max(ksmax, L.down.plan.ksplit);
+    b->part_cap = max_sessions * attention_states_bound(e->nkv_l);
+    int rc = 0;
+    auto A = [&](void **p, size_t bytes) {
+        if (rc) return;
+        rc = dev_alloc(p, bytes);
+        if (!rc) {
+            b->owned.push_back(*p);
+            hipMemset(*p, 0, bytes);
+        }
+    };
+    A((void **)&b->h, R * H * 2);
+    A((void **)&b->x, R * H * 2);
+    A((void **)&b->q, R * qd * 2);
+    A((void **)&b->attn, R * qd * 2);
+    A((void **)&b->act, R * I * 2);
+    A((void **)&b->xl, (size_t)16 * H * 2);
+    A((void **)&b->emb, (size_t)16 * H * 2);
+    A((void **)&b->partial, (size_t)ksmax * 16 * H * 4);
+    A((void **)&b->sq[0], (size_t)(512 + 16) * 16 * 4);
+    A((void **)&b->sq[1], (size_t)(512 + 16) * 16 * 4);
+    A((void **)&b->part_o, (size_t)b->part_cap * e->nh_l * 16 * hd * 4);
+    A((void **)&b->part_ml, (size_t)b->part_cap * e->nh_l * 16 * 2 * 4);
+    A((void **)&b->logits, (size_t)max_sessions * V * 2);
+    A((void **)&b->sample_scratch, (size_t)max_sessions * VLO_SAMPLE_SCRATCH_FLOATS * 4);
+    A((void **)&b->tok, (size_t)max_sessions * 8);
+    A((void **)&b->tables_dev, sizeof(BatchTables) * VLO_BATCH_SLOTS);
+    if (rc) {
+        vlo_batch_destroy(b);
+        return rc;
+    }
+    if (hipHostMalloc((void **)&b->host_tok, VLO_BATCH_MAX * 8, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void **)&b->stage, sizeof(BatchTables) * VLO_BATCH_SLOTS, hipHostMallocDefault) != hipSuccess) {
+        vlo_batch_destroy(b);
+        return fail(VLO_E_HIP, "hipHostMalloc failed");
+    }
+    for (hipEvent_t &ev : b->slot_ev)
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            vlo_batch_destroy(b);
+            return fail(VLO_E_HIP, "hipEventCreate failed");
+        }
+    HIP_TRY(hipDeviceSynchronize());
+    *out = b;
+    return VLO_OK;
+}
+
+void vlo_batch_destroy(vlo_batch *b) {
+    if (!b) return;
+    hipSetDevice(b->e->device);
+    hipDeviceSynchronize();
+    for (void *p : b->owned) hipFree(p);
+    if (b->host_tok) hipHostFree(b->host_tok);
+    if (b->stage) hipHostFree(b->stage);
+    for (hipEvent_t ev : b->slot_ev) if (ev) hipEventDestroy(ev);
+    delete b;
+}
+
+// the refusals every batched call shares
+static int batch_check(const vlo_batch *b, vlo_session *const *ss, int B, const int *n, int *rows_total) {
+    if (!b || !ss || !n) return fail(VLO_E_INVALID, "null argument");
+    if (B < 1 || B > b->max_sessions) return fail(VLO_E_INVALID, "batch of " + std::to_string(B) + " sessions (max_sessions " + std::to_string(b->max_sessions) + ")");
+    if (b->e->tp_size > 1) return fail(VLO_E_STATE, "tensor-parallel engine: batched steps are not supported");
+    int M = 0;
+    for (int i = 0; i < B; ++i) {
+        if (!ss[i]) return fail(VLO_E_INVALID, "null session " + std::to_string(i));
+        if (ss[i]->e != b->e) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " belongs to another engine");
+        for (int j = 0; j < i; ++j)
+            if (ss[j] == ss[i]) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " repeats session " + std::to_string(j));
+        if (n[i] < 1) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " appends " + std::to_string(n[i]) + " tokens (>= 1)");
+        M += n[i];
+    }
+    *rows_total = M;
+    return VLO_OK;
+}
+
+// KV pages of every session for its new length, all or nothing: no page is taken unless all fit (and whatever was taken goes back on failure)
+static int batch_pages(vlo_session *const *ss, int B, const int *n, hipStream_t st) {
+    vlo_engine *e = ss[0]->e;
+    int need = 0;
+    for (int i = 0; i < B; ++i) {
+        const int64_t L = ss[i]->len + n[i];
+        if (L > e->max_positions) return fail(VLO_E_NOMEM, "session " + std::to_string(i) + ": sequence exceeds kv_pool_tokens");
+        need += std::max(0, (int)((L + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS) - (int)ss[i]->pages.size());
+    }
+    {
+        std::lock_guard<std::mutex> g(e->pool_mu);
+        if ((int)e->free_pages.size() < need)
+            return fail(VLO_E_NOMEM, "KV pool exhausted: the batch needs " + std::to_string(need) + " pages, " + std::to_string(e->free_pages.size()) + " free");
+    }
+    size_t had[VLO_BATCH_MAX];
+    for (int i = 0; i < B; ++i) had[i] = ss[i]->pages.size();
+    for (int i = 0; i < B; ++i) {
+        const int rc = ensure_pages(ss[i], ss[i]->len + n[i], st);
+        if (rc) {                                      // another thread took pages in between: hand back what this call took
+            std::lock_guard<std::mutex> g(e->pool_mu);
+            for (int j = 0; j < i; ++j) {
+                for (size_t p = had[j]; p < ss[j]->pages.size(); ++p) e->free_pages.push_back(ss[j]->pages[p]);
+                ss[j]->pages.resize(had[j]);
+            }
+            return rc;
+        }
+    }
+    return VLO_OK;
+}
+
+int vlo_batch_step(vlo_batch *b, vlo_session *const *ss, int B, const void *embeds_dev, const int *n_host, void *last_logits_dev, void *stream) {
+    int M = 0, rc;
+    if ((rc = batch_check(b, ss, B, n_host, &M))) return rc;
+    if (!embeds_dev) return fail(VLO_E_INVALID, "null embeddings");
+    if (M > VLO_BLOCK_TOKENS) return fail(VLO_E_INVALID, "batch of " + std::to_string(M) + " rows: at most " + std::to_string(VLO_BLOCK_TOKENS) + " (split the batch)");
+    vlo_engine *e = b->e;
+    const vlo_config &c = e->cfg;
+    const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads, V = c.vocab_size;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = batch_pages(ss, B, n_host, st))) return rc;
+
+    // ---- this step's tables (slot k of the ring)
+    const int k = b->slot;
+    if (b->slot_used[k]) HIP_TRY(hipEventSynchronize(b->slot_ev[k]));      // the step that last used slot k has read it
+    BatchTables &T = b->stage[k];
+    const int *tables[VLO_BATCH_MAX];
+    int64_t lens[VLO_BATCH_MAX];
+    int rows[VLO_BATCH_MAX];
+    for (int i = 0, r = 0; i < B; ++i) {
+        const vlo_session *s = ss[i];
+        tables[i] = s->page_table;
+        lens[i] = s->len;
+        rows[i] = r;
+        for (int j = 0; j < n_host[i]; ++j, ++r) {
+            const int64_t pos = s->len + j;
+            T.rows[r].pos = (int)pos;
+            T.rows[r].page = s->pages[pos / VLO_PAGE_TOKENS];
+        }
+    }
+    const KvPool kv = kv_geom(ss[0]);                  // pool geometry (each segment / row carries its own pages)
+    AttnSegRun runs[4];
+    int nseg = 0, nrun = 0, states = 0;
+    HIP_TRY(attention_seg_plan(kv, nh, B, tables, lens, n_host, rows, b->part_cap, T.segs, &nseg, runs, &nrun, &states));
+    BatchTables *Td = b->tables_dev + k;
+    HIP_TRY(hipMemcpyAsync(Td, &T, sizeof(BatchTables), hipMemcpyHostToDevice, st));
+    KvPool kvr = kv;
+    kvr.page_table = reinterpret_cast<const int *>(Td->rows);   // EPI_ROPE_ROWS reads the row table through kv.page_table (gemv.h)
+
+    // ---- the decoder layers: run_chunk's sequence (M <= 16) or run_block's (17..64 rows)
+    const bool block = M > 16;
+    HIP_TRY(copy_rows_launch((const unsigned short *)embeds_dev, b->h, M, H, st));
+    const float *prev = nullptr;
+    int prev_ks = 0;
+    for (int l = 0; l < c.num_layers; ++l) {
+        const LayerWeights &L = e->layers[l];
+        HIP_TRY(add_rmsnorm_launch(b->h, prev, prev_ks, H, (const unsigned short *)L.ln_in, b->x, H, block ? 0 : H, c.rms_eps, M, st));
+        {   // qkv [RoPE + KV append at each row's own position and page]
+            GemvArgs a = gemv_args(L.qkv, b->x, H, M);
+            a.out_bf16 = b->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
+            a.layer = l; a.num_heads = nh; a.pos0 = 0;
+            const int epi = rope_epi(a, kvr) == EPI_ROPE_F8 ? EPI_ROPE_ROWS_F8 : EPI_ROPE_ROWS;
+            if (block) HIP_TRY(gemm64_launch(a, L.qkv.plan64, epi, st));
+            else HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
+        }
+        HIP_TRY(attention_seg_launch(b->q, kv, l, nh, Td->segs, nseg, runs, nrun, b->part_o, b->part_ml, b->attn, block, st));
+        if (block) {
+            {   // o_proj + residual
+                GemvArgs a = gemv_args(L.o, b->attn, nh * hd, M);
+                a.h = b->h; a.ldo = H;
+                HIP_TRY(gemm64_launch(a, L.o.plan64, EPI_RESID, st));
+            }
+            HIP_TRY(add_rmsnorm_launch(b->h, nullptr, 0, H, (const unsigned short *)L.ln_post, b->x, H, 0, c.rms_eps, M, st));
+            {   // gate/up + SwiGLU
+                GemvArgs a = gemv_args(L.gate_up, b->x, H, M);
+                a.out_bf16 = b->act; a.ldo = I;
+                HIP_TRY(gemm64_launch(a, L.gate_up.plan64, EPI_SWIGLU, st));
+            }
+            {   // down_proj + residual
+                GemvArgs a = gemv_args(L.down, b->act, I, M);
+                a.h = b->h; a.ldo = H;
+                HIP_TRY(gemm64_launch(a, L.down.plan64, EPI_RESID, st));
+            }
+            continue;
+        }
+        int sq_parts;
+        {   // o_proj + residual
+            GemvArgs a = gemv_args(L.o, b->attn, nh * hd, M);
+            a.h = b->h; a.ldo = H; a.sq_out = b->sq[0];
+            sq_parts = gemv_grid_x(a, L.o.plan, EPI_RESID);
+            HIP_TRY(gemv_launch(a, L.o.plan, XSRC_PLAIN, EPI_RESID, st));
+        }
+        {   // gate/up + SwiGLU
+            GemvArgs a = gemv_args(L.gate_up, b->h, H, M);
+            a.norm_w = (const unsigned short *)L.ln_post; a.sq_in = b->sq[0]; a.sq_in_parts = sq_parts; a.eps = c.rms_eps;
+            a.out_bf16 = b->act; a.ldo = I;
+            HIP_TRY(gemv_launch(a, L.gate_up.plan, XSRC_NORM, EPI_SWIGLU, st));
+        }
+        {   // down_proj: fp32 K-slice partials, combined by the next add_rmsnorm
+            GemvArgs a = gemv_args(L.down, b->act, I, M);
+            a.out_f32 = b->partial; a.ldo = H;
+            HIP_TRY(gemv_launch(a, L.down.plan, XSRC_PLAIN, EPI_PARTIAL_F32, st));
+            prev = b->partial;
+            prev_ks = L.down.plan.ksplit;
+        }
+    }
+    // ---- each session's last row: final norm, gathered into B rows, one lm_head pass, scattered to the sessions
+    HIP_TRY(add_rmsnorm_launch(b->h, prev, prev_ks, H, (const unsigned short *)e->norm_w, b->x, H, H, c.rms_eps, M, st));
+    RowCopy g{}, sc{};
+    for (int i = 0; i < B; ++i) {
+        g.src[i] = b->x + (size_t)(rows[i] + n_host[i] - 1) * H;
+        g.dst[i] = b->xl + (size_t)i * H;
+        sc.src[i] = b->logits + (size_t)i * V;
+        sc.dst[i] = ss[i]->logits;
+    }
+    HIP_TRY(copy_rows_indexed_launch(g, B, H, st));
+    {
+        GemvArgs a = gemv_args(e->lm_head, b->xl, H, B);
+        a.out_bf16 = b->logits; a.ldo = V;
+        HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
+    }
+    HIP_TRY(copy_rows_indexed_launch(sc, B, V, st));
+    if (last_logits_dev) HIP_TRY(hipMemcpyAsync(last_logits_dev, b->logits, (size_t)B * V * 2, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipEventRecord(b->slot_ev[k], st));
+    b->slot_used[k] = true;
+    b->slot = (k + 1) % VLO_BATCH_SLOTS;
+    for (int i = 0; i < B; ++i) {
+        vlo_session *s = ss[i];
+        s->last_logits = s->logits;
+        s->has_logits = true;
+        s->len += n_host[i];
+    }
+    b->last_B = B;
+    return VLO_OK;
+}
+
+int vlo_batch_stream_sample(vlo_batch *b, float threshold, int interval_id, int64_t *tok_dev, float *p_interval_dev, void *stream) {
+    if (!b || !tok_dev) return fail(VLO_E_INVALID, "bad batch_stream_sample arguments");
+    if (!b->last_B) return fail(VLO_E_STATE, "no logits: call vlo_batch_step first");
+    HIP_TRY(hipSetDevice(b->e->device));
+    HIP_TRY(stream_sample_rows_launch(b->logits, b->last_B, b->e->cfg.vocab_size, threshold, interval_id, tok_dev, p_interval_dev,
+                                      b->sample_scratch, (hipStream_t)stream));
+    return VLO_OK;
+}
+
+// Non-speculative: per decode step one batched argmax, one copy of the active sessions' tokens to the host, then the host drops the sessions
+// that are done and steps the others.  Each session's ids, length and logits end as vlo_greedy_generate leaves them (force_len = 0).
+int vlo_batch_greedy_generate(vlo_batch *b, vlo_session *const *ss, int B, const void *embeds_dev, const int *m_host, int eos_token_id,
+                              int64_t *out_ids_dev, int max_new, int *n_written_host, void *stream) {
+    int M = 0, rc;
+    if ((rc = batch_check(b, ss, B, m_host, &M))) return rc;
+    if (!embeds_dev || !out_ids_dev || !n_written_host || max_new <= 0) return fail(VLO_E_INVALID, "bad batch_greedy_generate arguments");
+    vlo_engine *e = b->e;
+    const int H = e->cfg.hidden_size, V = e->cfg.vocab_size;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<std::vector<int64_t>> ids(B);
+    auto finish = [&]() -> int {                   // the ids go to the caller's rows (each row's first n_written entries)
+        for (int i = 0; i < B; ++i) {
+            n_written_host[i] = (int)ids[i].size();
+            if (!ids[i].empty())
+                HIP_TRY(hipMemcpy(out_ids_dev + (size_t)i * max_new, ids[i].data(), ids[i].size() * 8, hipMemcpyHostToDevice));
+        }
+        b->last_B = 0;                             // the batch's logits rows no longer follow the sessions' order
+        return VLO_OK;
+    };
+    for (int i = 0; i < B; ++i) n_written_host[i] = 0;
+    if (M <= 16) {
+        if ((rc = vlo_batch_step(b, ss, B, embeds_dev, m_host, nullptr, stream))) return rc;
+    } else {                                       // long prefixes: each session's own vlo_llm_step, then its logits row into the batch's matrix
+        RowCopy g{};
+        for (int i = 0, r = 0; i < B; r += m_host[i], ++i) {
+            if ((rc = vlo_llm_step(ss[i], (const unsigned short *)embeds_dev + (size_t)r * H, m_host[i], nullptr, nullptr, stream))) return rc;
+            g.src[i] = ss[i]->last_logits;
+            g.dst[i] = b->logits + (size_t)i * V;
+        }
+        HIP_TRY(copy_rows_indexed_launch(g, B, V, st));
+    }
+    std::vector<vlo_session *> act(ss, ss + B);
+    std::vector<int> idx(B);
+    for (int i = 0; i < B; ++i) idx[i] = i;
+    for (int i = 0;; ++i) {
+        const int nA = (int)act.size();
+        HIP_TRY(greedy_sample_rows_launch(b->logits, nA, V, b->tok, b->sample_scratch, st));
+        HIP_TRY(hipMemcpyAsync(b->host_tok, b->tok, (size_t)nA * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<vlo_session *> keep;
+        std::vector<int> keep_idx;
+        StepIds next{};
+        for (int r = 0; r < nA; ++r) {
+            const int64_t t = b->host_tok[r];
+            ids[idx[r]].push_back(t);
+            if (t == eos_token_id) {
+                act[r]->has_logits = false;        // the EOS is not fed; the logits that produced it are consumed (vlo_greedy_generate)
+            } else if (i < max_new - 1) {
+                next.v[keep.size()] = t;
+                keep.push_back(act[r]);
+                keep_idx.push_back(idx[r]);
+            }
+        }
+        if (keep.empty()) break;
+        const int k = (int)keep.size();
+        HIP_TRY(step_input_launch((const unsigned short *)e->embed, next, k, nullptr, 0, H, V, b->emb, st));
+        const std::vector<int> ones(k, 1);
+        if ((rc = vlo_batch_step(b, keep.data(), k, b->emb, ones.data(), nullptr, stream))) {
+            const std::string msg = vlo_last_error();
+            finish();
+            return fail(rc, msg);
+        }
+        act.swap(keep);
+        idx.swap(keep_idx);
+    }
+    return finish();
+}
+
 // connector scratch (allocated outside any stream capture)
 int vlo_connector_reserve(vlo_engine *e) {
     if (e->conn_x) return VLO_OK;

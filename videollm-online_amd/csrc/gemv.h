@@ -15,9 +15,16 @@ enum {
     EPI_ROPE = 5,            // q/k/v split, RoPE, q buffer + paged K / V^T append   (qkv)
     EPI_PARTIAL_MBOX = 6,    // tensor parallel, ksplit == 1: a rank's o / down partial sums published as {epoch, fp32} granules straight into EVERY
                              // rank's p2p mailbox (tp.hip "p2p exchange"): no partial matrix in HBM, no publish pass in the exchange kernel
-    EPI_ROPE_F8 = 7          // EPI_ROPE appending to an fp8 e4m3 pool (llm_ops.h KvPool): K after RoPE and V quantised with kv_scale[layer]
+    EPI_ROPE_F8 = 7,         // EPI_ROPE appending to an fp8 e4m3 pool (llm_ops.h KvPool): K after RoPE and V quantised with kv_scale[layer]
+    EPI_ROPE_ROWS = 8,       // EPI_ROPE for rows of DIFFERENT sessions (batched step, engine.hip vlo_batch_step): row m takes its RoPE position and its
+                             // physical KV page from the row table RopeRow[m] that kv.page_table then points at (pos0 unused)
+    EPI_ROPE_ROWS_F8 = 9     // EPI_ROPE_ROWS appending to an fp8 e4m3 pool
 };
-constexpr bool epi_rope(int epi) { return epi == EPI_ROPE || epi == EPI_ROPE_F8; }
+constexpr bool epi_rope(int epi) { return epi == EPI_ROPE || epi == EPI_ROPE_F8 || epi == EPI_ROPE_ROWS || epi == EPI_ROPE_ROWS_F8; }
+constexpr bool epi_kv_f8(int epi) { return epi == EPI_ROPE_F8 || epi == EPI_ROPE_ROWS_F8; }
+constexpr bool epi_rows(int epi) { return epi == EPI_ROPE_ROWS || epi == EPI_ROPE_ROWS_F8; }
+// one row of the EPI_ROPE_ROWS table (device memory, int pairs): the token's position and the physical page its K / V^T land in
+struct RopeRow { int pos, page; };
 // activation operand source
 enum {
     XSRC_PLAIN = 0,          // x is a bf16 [16][ldx] tile

@@ -229,6 +229,8 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
     } else {
         if (epi == EPI_ROPE) VLO_GO(XSRC_PLAIN, EPI_ROPE);
         if (epi == EPI_ROPE_F8) VLO_GO(XSRC_PLAIN, EPI_ROPE_F8);
+        if (epi == EPI_ROPE_ROWS) VLO_GO(XSRC_PLAIN, EPI_ROPE_ROWS);
+        if (epi == EPI_ROPE_ROWS_F8) VLO_GO(XSRC_PLAIN, EPI_ROPE_ROWS_F8);
         if (epi == EPI_SWIGLU) VLO_GO(XSRC_PLAIN, EPI_SWIGLU);
         if (epi == EPI_RESID) VLO_GO(XSRC_PLAIN, EPI_RESID);
         if (epi == EPI_BF16) VLO_GO(XSRC_PLAIN, EPI_BF16);
@@ -243,7 +245,7 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
 hipError_t gemv_prepare(GemvArgs *a, const GemvPlan &p, int epi, int *grid_x, int *grid_y, size_t *lds_bytes) {
     if (epi != EPI_PARTIAL_F32 && p.ksplit != 1) return hipErrorInvalidValue;
     if (epi == EPI_PARTIAL_MBOX && (a->mbox_T < 1 || a->mbox_T > 8 || !a->mbox[0])) return hipErrorInvalidValue;
-    if (epi == EPI_ROPE_F8 && !a->kv_scale) return hipErrorInvalidValue;
+    if (epi_kv_f8(epi) && !a->kv_scale) return hipErrorInvalidValue;
     if (epi_rope(epi) && ((a->NT & 1) || (a->kv.head_dim != 64 && a->kv.head_dim != 128))) return hipErrorInvalidValue;
     a->CT = single_tile_groups(*a, p, epi) ? 1 : 2;
     a->KC = p.KC;

@@ -26,8 +26,16 @@
                     {
                         const int half = hd >> 1, nh = a.num_heads, nkv = a.kv.num_kv_heads;
                         const int head = g / hp, i = (g % hp) * 16 + (l >> 4) * 4;   // column inside the head, < half
-                        const long long pos = a.pos0 + m;
-                        const int page = a.kv.page_table[pos / VLO_PAGE_TOKENS];
+                        long long pos;
+                        int page;
+                        if constexpr (epi_rows(EPI)) {                    // batched step: the row's own position and page (gemv.h RopeRow)
+                            const RopeRow rr = reinterpret_cast<const RopeRow *>(a.kv.page_table)[m];
+                            pos = rr.pos;
+                            page = rr.page;
+                        } else {
+                            pos = a.pos0 + m;
+                            page = a.kv.page_table[pos / VLO_PAGE_TOKENS];
+                        }
                         const int tok = (int)(pos % VLO_PAGE_TOKENS);
                         if (head < nh + nkv) {
                             bf16_t *dst = (head < nh)
@@ -46,7 +54,7 @@
                                 lo[r] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
                                 hi[r] = f2bf(rbf(x2 * c) + rbf(x1 * s));
                             }
-                            if (EPI == EPI_ROPE_F8 && head >= nh) {
+                            if (epi_kv_f8(EPI) && head >= nh) {
                                 // fp8 pool: the bf16 K row quantised with the layer's k_scale, 4 + 4 bytes
                                 const float ks = a.kv_scale[2 * a.layer];
                                 uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.k_pool) + (size_t)a.layer * a.kv.layer_stride +
@@ -57,7 +65,7 @@
                                 *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
                                 *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
                             }
-                        } else if (EPI == EPI_ROPE_F8) {
+                        } else if (epi_kv_f8(EPI)) {
                             // fp8 V^T: this lane's 4 + 4 head-dim rows of one token are bytes VLO_PAGE_TOKENS apart; the 16 lanes of a row hold
                             // 16 consecutive tokens, so each byte store of the wave covers 16 adjacent bytes
                             const float vs = a.kv_scale[2 * a.layer + 1];

@@ -63,6 +63,38 @@ hipError_t attention_prefill_launch(const unsigned short *q, const KvPool &kv, i
 struct AttnGeom { int G, KS, hpw, nhg, nz, chunk, nsplit, nct; float scale; size_t lds_bytes; };
 hipError_t attention_geometry(const KvGeom &kv, int num_heads, int64_t pos0, int n, AttnGeom *g, int part_cap = VLO_MAX_SPLITS);
 
+// ---- batched steps (engine.hip vlo_batch_step): rows of several sessions in one launch ----------------------------------------------
+// One SEGMENT = one 16-query sub-chunk of one session: its own page table, cache position, query count, the split geometry that
+// attention_geometry gives that session stepped ALONE (so a batched row equals the solo row bit for bit), its first q / output row and
+// its first partial state.  The table lives in device memory (uploaded once per batch step, read by every layer).
+struct AttnSeg {
+    const int *page_table;       // the session's logical -> physical page table (device)
+    long long pos0;              // position of the sub-chunk's first query
+    int n;                       // queries (1..16)
+    int chunk, nsplit;           // the solo launch's split geometry
+    int row0;                    // first query row in q (row-major [rows][nh * hd]) and first output row (row-major, or packed-64 row)
+    int part0;                   // first partial state (units of [nh][16][hd] floats / [nh][16][2] floats)
+    int pad_;
+};
+// a run of segments whose solo launches take the same kernel (g.nct: attn_cols NCT, 0 = attn_chunk); max_nsplit = the launch's grid.x
+struct AttnSegRun { int first, count, max_nsplit; AttnGeom g; };
+#define VLO_ATTN_SEG_MAX 20      // segments of one batch step: <= 16 sessions, <= 64 rows (sum of ceil(n_b / 16) <= 16 + 3)
+// split states one session of n new tokens may take in the launch attention_geometry plans for it (the batch's partial buffers hold this many
+// per session)
+int attention_states_bound(int num_kv_heads);
+// plans the segments of B sessions (tables[b], lens[b] = cache length before the step, ns[b] new tokens, rows[b] = first row), grouped by
+// kernel family: segs[0 .. *nseg) (host copy of the device table), runs[0 .. *nrun), *states = partial states used.  part_cap: states available
+hipError_t attention_seg_plan(const KvGeom &kv, int num_heads, int B, const int *const *tables, const int64_t *lens, const int *ns,
+                              const int *rows, int part_cap, AttnSeg *segs, int *nseg, AttnSegRun *runs, int *nrun, int *states);
+// the planned launches + one segmented combine.  segs_dev = the device copy of the planned table; packed: `out` is packed-64 (block path)
+hipError_t attention_seg_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, const AttnSeg *segs_dev, int nseg,
+                                const AttnSegRun *runs, int nrun, float *part_o, float *part_ml, unsigned short *out, bool packed, hipStream_t st);
+// dst[i][0 .. cols) = src[i][0 .. cols) for i < count (bf16 rows anywhere in device memory, 16-byte aligned, cols % 8 == 0): gathers the
+// last row of each session of a batch, scatters the batch's logits rows to the sessions
+#define VLO_ROWCOPY_MAX 16
+struct RowCopy { const unsigned short *src[VLO_ROWCOPY_MAX]; unsigned short *dst[VLO_ROWCOPY_MAX]; };
+hipError_t copy_rows_indexed_launch(const RowCopy &rc, int count, int cols, hipStream_t st);
+
 hipError_t embed_gather_launch(const unsigned short *table, const int64_t *ids, int k, int H, int64_t vocab,
                                unsigned short *out, hipStream_t st);
 
@@ -73,6 +105,11 @@ hipError_t greedy_sample_launch(const unsigned short *logits, int V, int64_t *to
                                 float *scratch, hipStream_t st);
 hipError_t stream_sample_launch(const unsigned short *logits, int V, float threshold, int interval_id,
                                 int64_t *tok_out, float *p_interval_out, float *scratch, hipStream_t st);
+// the same for `rows` rows of bf16 logits [rows][V] in one launch sequence (grid.y = row; scratch: VLO_SAMPLE_SCRATCH_FLOATS per row,
+// tok_out / p_interval_out: one entry per row); each row's reduction order is the solo kernels', so its result equals theirs bit for bit
+hipError_t greedy_sample_rows_launch(const unsigned short *logits, int rows, int V, int64_t *tok_out, float *scratch, hipStream_t st);
+hipError_t stream_sample_rows_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,
+                                     float *p_interval_out, float *scratch, hipStream_t st);
 
 #define VLO_STEP_IDS_MAX 32
 struct StepIds { int64_t v[VLO_STEP_IDS_MAX]; };      // token ids handed to step_input_kernel by value (kernel arguments)

@@ -142,44 +142,7 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float *__restri
         else out += (size_t)z * 16 * nh * HD;
         qrow &= 15;
     }
-    const int c4 = t % CL, sl = t / CL;
-    float4 o[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int sp = sl + j * SL;
-        o[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (sp < nsplit) o[j] = *reinterpret_cast<const float4 *>(part_o + (((size_t)sp * nh + head) * 16 + qrow) * HD + c4 * 4);
-    }
-    float ms = -INFINITY, ls = 0.f;
-    if (lane < nsplit) {
-        const float2 ml = *reinterpret_cast<const float2 *>(part_ml + (((size_t)lane * nh + head) * 16 + qrow) * 2);
-        ms = ml.x;
-        ls = ml.y;
-    }
-    const float M = wave_max(ms);
-    const float wv = (ms == -INFINITY) ? 0.f : __expf(ms - M);       // 0 for lanes >= nsplit and for empty splits
-    const float Ltot = wave_sum(ls * wv);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const float wj = __shfl(wv, sl + j * SL, 64);
-        acc.x += o[j].x * wj; acc.y += o[j].y * wj; acc.z += o[j].z * wj; acc.w += o[j].w * wj;
-    }
-    red[sl * CL + c4] = acc;
-    __syncthreads();
-    if (t < CL) {
-        float4 r = red[t];
-#pragma unroll
-        for (int k2 = 1; k2 < SL; ++k2) {
-            const float4 v = red[k2 * CL + t];
-            r.x += v.x; r.y += v.y; r.z += v.z; r.w += v.w;
-        }
-        const int d = t * 4;
-        const size_t at = pack_row0 < 0 ? (size_t)qrow * nh * HD + (size_t)head * HD + d : vlo_pack64_elem(pack_row0 + qrow, head * HD + d);
-        ushort4 ov;
-        ov.x = f2bf(r.x / Ltot); ov.y = f2bf(r.y / Ltot); ov.z = f2bf(r.z / Ltot); ov.w = f2bf(r.w / Ltot);
-        *reinterpret_cast<ushort4 *>(out + at) = ov;
-    }
+#include "attn_combine_body.inc"
 }
 static hipError_t attn_combine_launch(const float *part_o, const float *part_ml, int nsplit, int nh, int hd, int n, unsigned short *out,
                                       int pack_row0, hipStream_t st) {
@@ -277,6 +240,8 @@ hipError_t attention_prefill_launch(const unsigned short *q, const KvPool &kv, i
     return hipErrorNotSupported;                 // the caller falls back to attention_launch
 }
 
+static constexpr int kAttnWantBlocks = 256;            // split target of attention_geometry: ~one block per CU (128 / 512 measured slower)
+static constexpr int kBlockSubchunks = 4;          // 16-query sub-chunks of a block-path step (64 rows)
 hipError_t attention_geometry(const KvGeom &kv, int num_heads, int64_t pos0, int n, AttnGeom *g, int part_cap) {
     const int nkv = kv.num_kv_heads, hd = kv.head_dim, G = num_heads / nkv;
     const int L = (int)(pos0 + n);
@@ -297,8 +262,7 @@ hipError_t attention_geometry(const KvGeom &kv, int num_heads, int64_t pos0, int
     }
     // splits: ~one block per CU at long context; every wave should see at least one 32-key block
     int target = (L + KS * 32 - 1) / (KS * 32);
-    constexpr int want_blocks = 256;                    // (128 / 512 measured slower)
-    const int want = (want_blocks + nkv * nz - 1) / (nkv * nz);
+    const int want = (kAttnWantBlocks + nkv * nz - 1) / (nkv * nz);
     if (target > want) target = want;
     if (target > VLO_MAX_SPLITS / nz) target = VLO_MAX_SPLITS / nz;      // (the merge kernel holds one split per lane; 0 for nz > 64: one split below)
     if (target > part_cap / nz) target = part_cap / nz;
@@ -387,6 +351,242 @@ hipError_t attention_launch(const unsigned short *q, const KvPool &kv, int layer
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return attn_combine_launch(part_o, part_ml, nsplit, num_heads, hd, n, out, pack_row0, st);
+}
+
+// ------------------------------------------------------------------------------------
+// Segmented attention (batched steps, engine.hip vlo_batch_step): blockIdx.z = one segment of the device table (llm_ops.h AttnSeg), i.e.
+// one 16-query sub-chunk of one session with its own page table, position, query count, first row and split geometry — the geometry the
+// session's solo launch would use, so each segment walks exactly the keys, splits and merges of that launch.  grid.x = the widest segment's
+// split count; the blocks past a segment's last split leave at once (a uniform exit: no barrier has been reached).  The bodies are the solo
+// kernels' .inc files; only the kernel parameters they read are re-pointed at the segment.
+// ------------------------------------------------------------------------------------
+#define VLO_SEG_PROLOGUE                                                                                  \
+    const AttnSeg sg = segs[blockIdx.z];                                                                  \
+    if ((int)blockIdx.x >= sg.nsplit) return;                                                             \
+    kv.page_table = sg.page_table;                                                                        \
+    const bf16_t *__restrict__ q = q_rows + (size_t)sg.row0 * nh * HD;                                    \
+    int64_t pos0 = sg.pos0;                                                                               \
+    int n = sg.n;                                                                                         \
+    const int chunk = sg.chunk;                                                                           \
+    float *__restrict__ part_o = part_o_all + (size_t)sg.part0 * nh * 16 * HD;                            \
+    float *__restrict__ part_ml = part_ml_all + (size_t)sg.part0 * nh * 16 * 2;
+
+template <int HD, int HPW>
+__global__ __launch_bounds__(512) void attn_chunk_seg_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G, int KS,
+                                                             const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
+                                                             float *__restrict__ part_ml_all) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
+    VLO_SEG_PROLOGUE
+#define VLO_ATTN_BX blockIdx.x
+#define VLO_ATTN_BY blockIdx.y
+#define VLO_ATTN_BZ 0
+#define VLO_ATTN_GX gridDim.x
+#define VLO_ATTN_EXIT return
+#define VLO_ATTN_F8 0
+#include "attn_body.inc"
+#undef VLO_ATTN_F8
+#undef VLO_ATTN_BX
+#undef VLO_ATTN_BY
+#undef VLO_ATTN_BZ
+#undef VLO_ATTN_GX
+#undef VLO_ATTN_EXIT
+}
+template <int HD, int HPW>
+__global__ __launch_bounds__(512) void attn_chunk_seg_f8_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G, int KS,
+                                                                const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
+                                                                float *__restrict__ part_ml_all, const float *__restrict__ kv_scale) {
+    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
+    VLO_SEG_PROLOGUE
+    scale *= kv_scale[2 * layer];
+    const float vscale = kv_scale[2 * layer + 1];
+#define VLO_ATTN_BX blockIdx.x
+#define VLO_ATTN_BY blockIdx.y
+#define VLO_ATTN_BZ 0
+#define VLO_ATTN_GX gridDim.x
+#define VLO_ATTN_EXIT return
+#define VLO_ATTN_F8 1
+#include "attn_body.inc"
+#undef VLO_ATTN_F8
+#undef VLO_ATTN_BX
+#undef VLO_ATTN_BY
+#undef VLO_ATTN_BZ
+#undef VLO_ATTN_GX
+#undef VLO_ATTN_EXIT
+}
+template <int HD, int NCT>
+__global__ __launch_bounds__(512) void attn_cols_seg_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G,
+                                                            const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
+                                                            float *__restrict__ part_ml_all) {
+    VLO_SEG_PROLOGUE
+#define VLO_ATTN_F8 0
+#include "attn_cols_body.inc"
+#undef VLO_ATTN_F8
+}
+template <int HD, int NCT>
+__global__ __launch_bounds__(512) void attn_cols_seg_f8_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G,
+                                                               const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
+                                                               float *__restrict__ part_ml_all, const float *__restrict__ kv_scale) {
+    VLO_SEG_PROLOGUE
+    scale *= kv_scale[2 * layer];
+    const float vscale = kv_scale[2 * layer + 1];
+#define VLO_ATTN_F8 1
+#include "attn_cols_body.inc"
+#undef VLO_ATTN_F8
+}
+#undef VLO_SEG_PROLOGUE
+
+// merge of the split partials of every segment: grid = (nh, 16, segments); query row r of segment s goes to row s.row0 + r
+template <int HD>
+__global__ __launch_bounds__(256) void attn_combine_seg_kernel(const float *__restrict__ part_o, const float *__restrict__ part_ml,
+                                                               const AttnSeg *__restrict__ segs, int nh, bf16_t *__restrict__ out, int packed) {
+    constexpr int CL = HD / 4, SL = 256 / CL, NJ = VLO_MAX_SPLITS / SL;
+    __shared__ float4 red[SL * CL];
+    const int head = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    const AttnSeg sg = segs[blockIdx.z];
+    const int qrow = blockIdx.y, nsplit = sg.nsplit;
+    if (qrow >= sg.n) return;
+    part_o += (size_t)sg.part0 * nh * 16 * HD;
+    part_ml += (size_t)sg.part0 * nh * 16 * 2;
+    const int pack_row0 = packed ? sg.row0 : -1;
+    if (!packed) out += (size_t)sg.row0 * nh * HD;
+#include "attn_combine_body.inc"
+}
+
+int attention_states_bound(int num_kv_heads) {
+    // attention_geometry: nsplit <= ceil(kAttnWantBlocks / (nkv * nz)) for nz sub-chunks, and nz * nsplit <= VLO_MAX_SPLITS
+    const int b = (kAttnWantBlocks + num_kv_heads - 1) / num_kv_heads + kBlockSubchunks;
+    return b < VLO_MAX_SPLITS ? b : VLO_MAX_SPLITS;
+}
+
+hipError_t attention_seg_plan(const KvGeom &kv, int num_heads, int B, const int *const *tables, const int64_t *lens, const int *ns,
+                              const int *rows, int part_cap, AttnSeg *segs, int *nseg, AttnSegRun *runs, int *nrun, int *states) {
+    AttnSeg all[VLO_ATTN_SEG_MAX];
+    int fam[VLO_ATTN_SEG_MAX];
+    AttnGeom geo[VLO_ATTN_SEG_MAX];
+    int cnt = 0, part = 0;
+    for (int b = 0; b < B; ++b) {
+        AttnGeom g;
+        const hipError_t e = attention_geometry(kv, num_heads, lens[b], ns[b], &g);
+        if (e != hipSuccess) return e;
+        if (g.nz > kBlockSubchunks) return hipErrorInvalidValue;
+        for (int z = 0; z < g.nz; ++z) {
+            if (cnt == VLO_ATTN_SEG_MAX) return hipErrorInvalidValue;
+            AttnSeg &s = all[cnt];
+            s.page_table = tables[b];
+            s.pos0 = lens[b] + 16 * z;
+            s.n = ns[b] - 16 * z < 16 ? ns[b] - 16 * z : 16;
+            s.chunk = g.chunk;
+            s.nsplit = g.nsplit;
+            s.row0 = rows[b] + 16 * z;
+            s.part0 = part + z * g.nsplit;          // the solo launch's layout: sub-chunk z's states follow sub-chunk z - 1's
+            s.pad_ = 0;
+            fam[cnt] = g.nct;
+            geo[cnt] = g;
+            ++cnt;
+        }
+        part += g.nz * g.nsplit;
+    }
+    if (part > part_cap) return hipErrorInvalidValue;
+    int k = 0, r = 0;
+    for (int f = 0; f <= 3; ++f) {                  // one launch per kernel family: attn_chunk, attn_cols NCT = 1, 2, 3
+        const int first = k;
+        int mx = 0;
+        for (int i = 0; i < cnt; ++i)
+            if (fam[i] == f) {
+                segs[k++] = all[i];
+                if (all[i].nsplit > mx) mx = all[i].nsplit;
+                if (k - first == 1) runs[r].g = geo[i];
+            }
+        if (k > first) {
+            runs[r].first = first;
+            runs[r].count = k - first;
+            runs[r].max_nsplit = mx;
+            ++r;
+        }
+    }
+    *nseg = cnt;
+    *nrun = r;
+    *states = part;
+    return hipSuccess;
+}
+
+hipError_t attention_seg_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, const AttnSeg *segs_dev, int nseg,
+                                const AttnSegRun *runs, int nrun, float *part_o, float *part_ml, unsigned short *out, bool packed, hipStream_t st) {
+    const int nkv = kv.num_kv_heads, hd = kv.head_dim;
+    const bool f8 = kv.dtype == VLO_KV_FP8;
+    if (f8 && !kv.scale) return hipErrorInvalidValue;
+    if (nseg < 1 || nseg > VLO_ATTN_SEG_MAX) return hipErrorInvalidValue;
+    static bool attr_done = false;
+    if (!attr_done) {
+#define VLO_SEG_ATTR(K) (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+        VLO_SEG_ATTR((attn_chunk_seg_kernel<128, 2>)); VLO_SEG_ATTR((attn_chunk_seg_kernel<128, 1>));
+        VLO_SEG_ATTR((attn_chunk_seg_kernel<64, 2>)); VLO_SEG_ATTR((attn_chunk_seg_kernel<64, 1>));
+        VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<128, 2>)); VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<128, 1>));
+        VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<64, 2>)); VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<64, 1>));
+        VLO_SEG_ATTR((attn_cols_seg_kernel<128, 1>)); VLO_SEG_ATTR((attn_cols_seg_kernel<128, 2>)); VLO_SEG_ATTR((attn_cols_seg_kernel<128, 3>));
+        VLO_SEG_ATTR((attn_cols_seg_kernel<64, 1>)); VLO_SEG_ATTR((attn_cols_seg_kernel<64, 2>)); VLO_SEG_ATTR((attn_cols_seg_kernel<64, 3>));
+        VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 1>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 2>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 3>));
+        VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 1>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 2>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 3>));
+#undef VLO_SEG_ATTR
+        (void)hipGetLastError();
+        attr_done = true;
+    }
+    const KvGeom &kg = kv;
+    for (int r = 0; r < nrun; ++r) {
+        const AttnGeom &g = runs[r].g;
+        const AttnSeg *sd = segs_dev + runs[r].first;
+        const dim3 grid(runs[r].max_nsplit, nkv, runs[r].count);
+        const size_t lds = g.lds_bytes;
+        if (g.nct) {
+#define VLO_SEG_COLS(HD_, NCT_)                                                                                                          \
+    do {                                                                                                                                 \
+        if (f8) hipLaunchKernelGGL((attn_cols_seg_f8_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd,     \
+                                   g.scale, part_o, part_ml, kv.scale);                                                                  \
+        else hipLaunchKernelGGL((attn_cols_seg_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd, g.scale,  \
+                                part_o, part_ml);                                                                                        \
+    } while (0)
+            if (hd == 128 && g.nct == 1) VLO_SEG_COLS(128, 1);
+            else if (hd == 128 && g.nct == 2) VLO_SEG_COLS(128, 2);
+            else if (hd == 128) VLO_SEG_COLS(128, 3);
+            else if (g.nct == 1) VLO_SEG_COLS(64, 1);
+            else if (g.nct == 2) VLO_SEG_COLS(64, 2);
+            else VLO_SEG_COLS(64, 3);
+#undef VLO_SEG_COLS
+        } else {
+            const dim3 block(g.nhg * g.KS * 64);
+#define VLO_SEG_CHUNK(HD_, HPW_)                                                                                                          \
+    do {                                                                                                                                  \
+        if (f8) hipLaunchKernelGGL((attn_chunk_seg_f8_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd,   \
+                                   g.scale, part_o, part_ml, kv.scale);                                                                   \
+        else hipLaunchKernelGGL((attn_chunk_seg_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd, g.scale, \
+                                part_o, part_ml);                                                                                         \
+    } while (0)
+            if (hd == 128 && g.hpw == 2) VLO_SEG_CHUNK(128, 2);
+            else if (hd == 128 && g.hpw == 1) VLO_SEG_CHUNK(128, 1);
+            else if (hd == 64 && g.hpw == 2) VLO_SEG_CHUNK(64, 2);
+            else if (hd == 64 && g.hpw == 1) VLO_SEG_CHUNK(64, 1);
+            else return hipErrorInvalidValue;
+#undef VLO_SEG_CHUNK
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (hd == 128) hipLaunchKernelGGL(attn_combine_seg_kernel<128>, dim3(num_heads, 16, nseg), dim3(256), 0, st, part_o, part_ml, segs_dev, num_heads, out, (int)packed);
+    else if (hd == 64) hipLaunchKernelGGL(attn_combine_seg_kernel<64>, dim3(num_heads, 16, nseg), dim3(256), 0, st, part_o, part_ml, segs_dev, num_heads, out, (int)packed);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// dst[i] = src[i] (bf16 rows of `cols` elements): one block per row
+__global__ void copy_rows_indexed_kernel(RowCopy rc, int n16) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(rc.src[blockIdx.x]);
+    uint4 *dst = reinterpret_cast<uint4 *>(rc.dst[blockIdx.x]);
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+}
+hipError_t copy_rows_indexed_launch(const RowCopy &rc, int count, int cols, hipStream_t st) {
+    if (count < 1 || count > VLO_ROWCOPY_MAX || (cols & 7)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(copy_rows_indexed_kernel, dim3(count), dim3(256), 0, st, rc, cols / 8);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------
@@ -519,36 +719,28 @@ VLO_DEV ArgBest block_argbest(ArgBest x, float *smv, int *smi) {
 
 // scratch layout (floats): [0, NB) block max | [NB, 2NB) block sum of exp(x - block max) | [2NB, 3NB) best value |
 //                          [3NB, 4NB) best index (int bits)
+// Every kernel has a grid.y = row twin for batched steps that runs the SAME body (a textual include or a shared device function) on its row,
+// so a row's reduction order is the solo kernel's.
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_stats_kernel(const bf16_t *__restrict__ logits, int V, float *__restrict__ scr) {
     __shared__ float sm[16];
     __shared__ float smv[16];
     __shared__ int smi[16];
-    const int per = (V + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = min(V, lo + per);
-    float mx = -INFINITY;
-    ArgBest b = {-INFINITY, 0x7fffffff};
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        const float v = bf2f(logits[i]);
-        mx = fmaxf(mx, v);
-        if (v > b.v) { b.v = v; b.i = i; }
-    }
-    mx = block_max(mx, sm);
-    float s = 0.f;
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) s += expf(bf2f(logits[i]) - mx);
-    s = block_sum(s, sm);
-    b = block_argbest(b, smv, smi);
-    if (threadIdx.x == 0) {
-        const int NB = gridDim.x;
-        scr[blockIdx.x] = mx;
-        scr[NB + blockIdx.x] = (mx == -INFINITY) ? 0.f : s;
-        scr[2 * NB + blockIdx.x] = b.v;
-        reinterpret_cast<int *>(scr)[3 * NB + blockIdx.x] = b.i;
-    }
+#include "sample_stats_body.inc"
+}
+
+// rows x V logits: row blockIdx.y, scratch VLO_SAMPLE_SCRATCH_FLOATS per row
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_stats_rows_kernel(const bf16_t *__restrict__ logits_rows, int V, float *__restrict__ scr_rows) {
+    __shared__ float sm[16];
+    __shared__ float smv[16];
+    __shared__ int smi[16];
+    const bf16_t *__restrict__ logits = logits_rows + (size_t)blockIdx.y * V;
+    float *__restrict__ scr = scr_rows + (size_t)blockIdx.y * VLO_SAMPLE_SCRATCH_FLOATS;
+#include "sample_stats_body.inc"
 }
 
 // force_mode: 0 = plain argmax; 1 = argmax but never eos (scheduled mode, mid-response);
 //             2 = argmax computed, eos written (scheduled mode, last token)
-__global__ __launch_bounds__(64) void greedy_final_kernel(const float *__restrict__ scr, int NB, int V, int64_t *tok_out, int eos,
-                                                          int force_mode) {
+VLO_DEV void greedy_final_body(const float *__restrict__ scr, int NB, int V, int64_t *tok_out, int eos, int force_mode) {
     ArgBest b = {-INFINITY, 0x7fffffff};
     for (int k = threadIdx.x; k < NB; k += 64) b = better(b, (ArgBest){scr[2 * NB + k], reinterpret_cast<const int *>(scr)[3 * NB + k]});
     b = wave_argbest(b);
@@ -559,10 +751,23 @@ __global__ __launch_bounds__(64) void greedy_final_kernel(const float *__restric
         *tok_out = t;
     }
 }
+__global__ __launch_bounds__(64) void greedy_final_kernel(const float *__restrict__ scr, int NB, int V, int64_t *tok_out, int eos,
+                                                          int force_mode) {
+    greedy_final_body(scr, NB, V, tok_out, eos, force_mode);
+}
+__global__ __launch_bounds__(64) void greedy_final_rows_kernel(const float *__restrict__ scr, int NB, int V, int64_t *tok_out) {
+    greedy_final_body(scr + (size_t)blockIdx.y * VLO_SAMPLE_SCRATCH_FLOATS, NB, V, tok_out + blockIdx.y, 0, 0);
+}
 hipError_t greedy_sample_launch(const unsigned short *logits, int V, int64_t *tok_out, int eos, int force_mode, float *scratch,
                                 hipStream_t st) {
     hipLaunchKernelGGL(sample_stats_kernel, dim3(SAMPLE_BLOCKS), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
     hipLaunchKernelGGL(greedy_final_kernel, dim3(1), dim3(64), 0, st, scratch, SAMPLE_BLOCKS, V, tok_out, eos, force_mode);
+    return hipGetLastError();
+}
+hipError_t greedy_sample_rows_launch(const unsigned short *logits, int rows, int V, int64_t *tok_out, float *scratch, hipStream_t st) {
+    if (rows < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_stats_rows_kernel, dim3(SAMPLE_BLOCKS, rows), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
+    hipLaunchKernelGGL(greedy_final_rows_kernel, dim3(1, rows), dim3(64), 0, st, scratch, SAMPLE_BLOCKS, V, tok_out);
     return hipGetLastError();
 }
 
@@ -572,28 +777,17 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void stream_scan_kernel(const bf16_
                                                                      int interval_id, float *__restrict__ scr) {
     __shared__ float smv[16];
     __shared__ int smi[16];
-    const int NB = gridDim.x;
-    float M = -INFINITY;
-    for (int k = 0; k < NB; ++k) M = fmaxf(M, scr[k]);
-    float S = 0.f;
-    for (int k = 0; k < NB; ++k) S += scr[NB + k] * expf(scr[k] - M);
-    const float p_int = rbf(expf(bf2f(logits[interval_id]) - M) / S);
-    const bool zero_int = p_int < rbf(threshold);   // torch compares a bf16 tensor with a Python float in bf16
-    const int per = (V + NB - 1) / NB, lo = blockIdx.x * per, hi = min(V, lo + per);
-    ArgBest b = {-INFINITY, 0x7fffffff};
-    for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        float p = rbf(expf(bf2f(logits[i]) - M) / S);
-        if (i == interval_id && zero_int) p = 0.f;
-        if (p > b.v) { b.v = p; b.i = i; }
-    }
-    b = block_argbest(b, smv, smi);
-    if (threadIdx.x == 0) {
-        scr[4 * NB + blockIdx.x] = b.v;
-        reinterpret_cast<int *>(scr)[5 * NB + blockIdx.x] = b.i;
-        if (blockIdx.x == 0) scr[6 * NB] = p_int;
-    }
+#include "stream_scan_body.inc"
 }
-__global__ __launch_bounds__(64) void stream_final_kernel(const float *__restrict__ scr, int NB, int64_t *tok_out, float *p_interval_out) {
+__global__ __launch_bounds__(SAMPLE_THREADS) void stream_scan_rows_kernel(const bf16_t *__restrict__ logits_rows, int V, float threshold,
+                                                                          int interval_id, float *__restrict__ scr_rows) {
+    __shared__ float smv[16];
+    __shared__ int smi[16];
+    const bf16_t *__restrict__ logits = logits_rows + (size_t)blockIdx.y * V;
+    float *__restrict__ scr = scr_rows + (size_t)blockIdx.y * VLO_SAMPLE_SCRATCH_FLOATS;
+#include "stream_scan_body.inc"
+}
+VLO_DEV void stream_final_body(const float *__restrict__ scr, int NB, int64_t *tok_out, float *p_interval_out) {
     ArgBest b = {-INFINITY, 0x7fffffff};
     for (int k = threadIdx.x; k < NB; k += 64) b = better(b, (ArgBest){scr[4 * NB + k], reinterpret_cast<const int *>(scr)[5 * NB + k]});
     b = wave_argbest(b);
@@ -602,12 +796,27 @@ __global__ __launch_bounds__(64) void stream_final_kernel(const float *__restric
         if (p_interval_out) *p_interval_out = scr[6 * NB];
     }
 }
+__global__ __launch_bounds__(64) void stream_final_kernel(const float *__restrict__ scr, int NB, int64_t *tok_out, float *p_interval_out) {
+    stream_final_body(scr, NB, tok_out, p_interval_out);
+}
+__global__ __launch_bounds__(64) void stream_final_rows_kernel(const float *__restrict__ scr, int NB, int64_t *tok_out, float *p_interval_out) {
+    const int r = blockIdx.y;
+    stream_final_body(scr + (size_t)r * VLO_SAMPLE_SCRATCH_FLOATS, NB, tok_out + r, p_interval_out ? p_interval_out + r : nullptr);
+}
 hipError_t stream_sample_launch(const unsigned short *logits, int V, float threshold, int interval_id, int64_t *tok_out,
                                 float *p_interval_out, float *scratch, hipStream_t st) {
     if (interval_id < 0 || interval_id >= V) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_stats_kernel, dim3(SAMPLE_BLOCKS), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
     hipLaunchKernelGGL(stream_scan_kernel, dim3(SAMPLE_BLOCKS), dim3(SAMPLE_THREADS), 0, st, logits, V, threshold, interval_id, scratch);
     hipLaunchKernelGGL(stream_final_kernel, dim3(1), dim3(64), 0, st, scratch, SAMPLE_BLOCKS, tok_out, p_interval_out);
+    return hipGetLastError();
+}
+hipError_t stream_sample_rows_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,
+                                     float *p_interval_out, float *scratch, hipStream_t st) {
+    if (interval_id < 0 || interval_id >= V || rows < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_stats_rows_kernel, dim3(SAMPLE_BLOCKS, rows), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
+    hipLaunchKernelGGL(stream_scan_rows_kernel, dim3(SAMPLE_BLOCKS, rows), dim3(SAMPLE_THREADS), 0, st, logits, V, threshold, interval_id, scratch);
+    hipLaunchKernelGGL(stream_final_rows_kernel, dim3(1, rows), dim3(64), 0, st, scratch, SAMPLE_BLOCKS, tok_out, p_interval_out);
     return hipGetLastError();
 }
 

@@ -145,8 +145,16 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
                 const float va[4] = {sA.x, sA.y, sA.z, sA.w}, vb[4] = {sB.x, sB.y, sB.z, sB.w};
                 const int half = hd >> 1, nh = a.num_heads, nkv = a.kv.num_kv_heads;
                 const int head = g / hp, i = (g % hp) * 16 + (l >> 4) * 4;           // column inside the head, < half
-                const long long pos = a.pos0 + m;
-                const int page = a.kv.page_table[pos / VLO_PAGE_TOKENS];
+                long long pos;
+                int page;
+                if constexpr (epi_rows(EPI)) {                    // batched step: the row's own position and page (gemv.h RopeRow)
+                    const RopeRow rr = reinterpret_cast<const RopeRow *>(a.kv.page_table)[m];
+                    pos = rr.pos;
+                    page = rr.page;
+                } else {
+                    pos = a.pos0 + m;
+                    page = a.kv.page_table[pos / VLO_PAGE_TOKENS];
+                }
                 const int tok = (int)(pos % VLO_PAGE_TOKENS);
                 if (head < nh + nkv) {
                     bf16_t *dst = (head < nh)
@@ -164,7 +172,7 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
                         lo[r] = f2bf(rbf(x1 * cs) + rbf(-x2 * sn));                // q*cos + rotate_half(q)*sin, bf16 at every op
                         hi[r] = f2bf(rbf(x2 * cs) + rbf(x1 * sn));
                     }
-                    if (EPI == EPI_ROPE_F8 && head >= nh) {                 // fp8 pool (gemv_epi.inc): K row quantised with k_scale
+                    if (epi_kv_f8(EPI) && head >= nh) {                 // fp8 pool (gemv_epi.inc): K row quantised with k_scale
                         const float ks = a.kv_scale[2 * a.layer];
                         uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.k_pool) + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
                                       ((size_t)(head - nh) * VLO_PAGE_TOKENS + tok) * hd;
@@ -174,7 +182,7 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
                         *reinterpret_cast<ushort4 *>(dst + i) = *reinterpret_cast<const ushort4 *>(lo);
                         *reinterpret_cast<ushort4 *>(dst + half + i) = *reinterpret_cast<const ushort4 *>(hi);
                     }
-                } else if (EPI == EPI_ROPE_F8) {                            // fp8 V^T: byte stores, 16 consecutive tokens per row of the wave
+                } else if (epi_kv_f8(EPI)) {                            // fp8 V^T: byte stores, 16 consecutive tokens per row of the wave
                     const float vs = a.kv_scale[2 * a.layer + 1];
                     uint8_t *d8 = reinterpret_cast<uint8_t *>(a.kv.vt_pool) + (size_t)a.layer * a.kv.layer_stride + (size_t)page * a.kv.page_elems +
                                   ((size_t)(head - nh - nkv) * hd) * VLO_PAGE_TOKENS + tok;
@@ -267,6 +275,8 @@ static hipError_t launch64(const GemvArgs &a, int epi, dim3 grid, dim3 block, si
     } while (0)
     if (epi == EPI_ROPE) VLO_GO64(EPI_ROPE);
     if (epi == EPI_ROPE_F8) VLO_GO64(EPI_ROPE_F8);
+    if (epi == EPI_ROPE_ROWS) VLO_GO64(EPI_ROPE_ROWS);
+    if (epi == EPI_ROPE_ROWS_F8) VLO_GO64(EPI_ROPE_ROWS_F8);
     if (epi == EPI_SWIGLU) VLO_GO64(EPI_SWIGLU);
     if (epi == EPI_RESID) VLO_GO64(EPI_RESID);
     if (epi == EPI_BF16) VLO_GO64(EPI_BF16);
@@ -276,7 +286,7 @@ static hipError_t launch64(const GemvArgs &a, int epi, dim3 grid, dim3 block, si
 
 hipError_t gemm64_launch(GemvArgs a, const Gemm64Plan &p, int epi, hipStream_t st) {
     if (a.n_rows <= 0 || a.n_rows > VLO_BLOCK_TOKENS) return hipErrorInvalidValue;
-    if (epi == EPI_ROPE_F8 && !a.kv_scale) return hipErrorInvalidValue;
+    if (epi_kv_f8(epi) && !a.kv_scale) return hipErrorInvalidValue;
     if (epi_rope(epi) && ((a.NT & 1) || (a.kv.head_dim != 64 && a.kv.head_dim != 128))) return hipErrorInvalidValue;
     a.KC = p.KC;
     // single column tiles when pairs would leave most CUs without work (o_proj / down_proj: 256 tiles)

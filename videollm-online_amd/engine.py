@@ -136,6 +136,77 @@ class Session:
         return out
 
 
+class Batch:
+    """Workspace of batched steps (include/vlo.h vlo_batch_*): the live steps of up to ``max_sessions`` sessions of one engine in one
+    weight pass.  The sessions stay independent of the batch: each may be stepped alone, forked or cropped between batched steps."""
+
+    def __init__(self, engine: "Engine", max_sessions: int):
+        self.engine = engine
+        h = C.c_void_p()
+        _C.check(_C.lib().vlo_batch_create(engine._h, max_sessions, C.byref(h)))
+        self._h = h
+        self.max_sessions = max_sessions
+        self._last_B = 0                        # rows of the last step (what stream_sample samples)
+        engine._sessions.add(self)              # borrows the engine like a session: closed before it
+
+    def close(self):
+        if self._h:
+            _C.lib().vlo_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _handles(sessions):
+        return (C.c_void_p * len(sessions))(*[s._h.value for s in sessions])
+
+    def _rows(self, embeds_list):
+        H = self.engine.cfg.hidden_size
+        rows = [e.to(device=self.engine.device, dtype=torch.bfloat16).reshape(-1, H) for e in embeds_list]
+        return torch.cat(rows).contiguous(), (C.c_int * len(rows))(*[r.shape[0] for r in rows])
+
+    def step(self, sessions: list, embeds_list: list, want_last=True, stream=None):
+        """Appends embeds_list[b] ([n_b, H]) to sessions[b] for every b in one weight pass (sum n_b <= 64).  Returns the sessions'
+        last-row logits [B, V] bf16, or None."""
+        x, n = self._rows(embeds_list)
+        B = len(sessions)
+        last = torch.empty(B, self.engine.cfg.vocab_size, dtype=torch.bfloat16, device=self.engine.device) if want_last else None
+        _C.check(_C.lib().vlo_batch_step(self._h, self._handles(sessions), B, _ptr(x), n, _ptr(last) if want_last else None,
+                                         _stream_handle(stream)))
+        self._last_B = B
+        return last
+
+    def stream_sample(self, threshold: float, interval_id: int, stream=None):
+        """Engine.stream_sample on every row of the last step: (tok int64 [B], p_interval f32 [B])."""
+        B = self._last_B
+        tok = torch.empty(B, dtype=torch.long, device=self.engine.device)
+        p = torch.empty(B, dtype=torch.float32, device=self.engine.device)
+        _C.check(_C.lib().vlo_batch_stream_sample(self._h, threshold, interval_id, _ptr(tok), _ptr(p), _stream_handle(stream)))
+        return tok, p
+
+    def greedy_generate(self, sessions: list, embeds_list: list, eos_token_id: int, inplace_output_ids_list: list, stream=None) -> list:
+        """Engine.greedy_generate for every session at once; inplace_output_ids_list[b] (int64, on the device, contiguous) receives
+        session b's ids, max_new = the shortest of them.  Returns the number of ids written per session."""
+        x, m = self._rows(embeds_list)
+        B = len(sessions)
+        for t in inplace_output_ids_list:
+            assert t.dtype == torch.long and t.is_cuda and t.is_contiguous()
+        max_new = min(t.numel() for t in inplace_output_ids_list)
+        out = torch.empty(B, max_new, dtype=torch.long, device=self.engine.device)
+        n = (C.c_int * B)()
+        _C.check(_C.lib().vlo_batch_greedy_generate(self._h, self._handles(sessions), B, _ptr(x), m, eos_token_id, _ptr(out), max_new, n,
+                                                    _stream_handle(stream)))
+        self._last_B = 0
+        for b in range(B):
+            if n[b]:
+                inplace_output_ids_list[b][:n[b]].copy_(out[b, :n[b]])
+        return list(n)
+
+
 class Engine:
     def __init__(self, cfg: EngineConfig, device: int | str | torch.device = 0):
         if not torch.cuda.is_available():
@@ -207,6 +278,9 @@ class Engine:
 
     def new_session(self, max_tokens_hint: int = 0) -> Session:
         return Session(self, max_tokens_hint)
+
+    def new_batch(self, max_sessions: int) -> Batch:
+        return Batch(self, max_sessions)
 
     def close(self):
         if self._h:
