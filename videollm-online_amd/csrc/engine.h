@@ -98,15 +98,25 @@ struct vlo_engine {
     double prof_ms = 0.0;
 };
 
+// What one pass over the decoder layers writes (engine.hip decoder_layers).  The 16-row pipeline keeps every matrix row-major; the 64-token
+// block path keeps x, attn and act packed-64 (llm_ops.h) and does not use partial / sq.
+struct StepWs {
+    unsigned short *h = nullptr, *x = nullptr, *q = nullptr, *attn = nullptr, *act = nullptr;   // residual stream, normed rows, q after RoPE, attention out, MLP act
+    float *partial = nullptr;                    // down-proj split-K partial sums [ksplit][16][H], combined by the next add_rmsnorm
+    float *sq[2] = {nullptr, nullptr};           // row sum-of-squares partials handed from EPI_RESID to XSRC_NORM
+    float *part_o = nullptr, *part_ml = nullptr; // split-KV attention partial states: part_cap of [nh][16][hd] / [nh][16][2] floats
+    int part_cap = 0;
+};
+
 struct vlo_session {
     vlo_engine *e = nullptr;
     int64_t len = 0;
     bool has_logits = false;
     std::vector<int> pages;
     std::vector<void *> owned;
-    unsigned short *h = nullptr, *x = nullptr, *act = nullptr, *attn = nullptr, *q = nullptr, *emb1 = nullptr;
-    float *part_o = nullptr, *part_ml = nullptr, *partial = nullptr;
-    float *sq[2] = {nullptr, nullptr};          // row sum-of-squares partials handed from EPI_RESID to XSRC_NORM
+    StepWs ws;                                   // the 16-row pipeline's set (h, x, act, attn: 32 rows; q: 16)
+    StepWs bws;                                  // the 64-token block path's set: allocated on first use, shares ws's attention partials
+    unsigned short *emb1 = nullptr;
     unsigned short *logits = nullptr, *last_logits = nullptr;
     unsigned short *logits_local = nullptr;      // TP: this rank's vocabulary shard [16][V_l]
     float *partial_o = nullptr;                  // TP: o_proj partial sums [16][H] awaiting the all-reduce
@@ -115,8 +125,6 @@ struct vlo_session {
     int64_t *host_tok = nullptr;                 // pinned, 8 slots: tokens read back by the greedy loop (double-buffered)
     hipEvent_t tok_ev[2] = {nullptr, nullptr};   // "token i is on the host" (created on first use)
     int *page_table = nullptr, *host_pt = nullptr;
-    // workspaces of the 64-token block path (allocated on first use): residual stream, normed rows, q, attention out, MLP act
-    unsigned short *bh = nullptr, *bx = nullptr, *bq = nullptr, *battn = nullptr, *bact = nullptr;
     // workspaces of the prefill path (blocks of up to VLO_PREFILL_TOKENS tokens as real GEMMs, prefill.h; allocated on first use):
     // residual stream, normed rows / attention output (the GEMMs' X operand: 256 spare rows), qkv projection, q after RoPE, MLP act
     unsigned short *ph = nullptr, *px = nullptr, *pqkv = nullptr, *pq = nullptr, *pact = nullptr;
@@ -144,13 +152,9 @@ struct vlo_batch {
     vlo_engine *e = nullptr;
     int max_sessions = 0;
     std::vector<void *> owned;
-    // activations of up to 64 rows; the 16-row pipeline uses them row-major, the block path as run_block does (x, attn, act packed-64)
-    unsigned short *h = nullptr, *x = nullptr, *q = nullptr, *attn = nullptr, *act = nullptr;
+    StepWs ws;                                   // up to 64 rows, serving both layouts; part_cap = max_sessions * attention_states_bound(nkv)
     unsigned short *xl = nullptr;                // [16][H]: the normed last row of each session, the lm_head's input
     unsigned short *emb = nullptr;               // [16][H]: the next step's input rows of the greedy loop
-    float *partial = nullptr, *sq[2] = {nullptr, nullptr};
-    float *part_o = nullptr, *part_ml = nullptr; // split-KV partial states: max_sessions * attention_states_bound(nkv)
-    int part_cap = 0;
     unsigned short *logits = nullptr;            // [max_sessions][V]: row b = session b of the last step
     float *sample_scratch = nullptr;             // [max_sessions][VLO_SAMPLE_SCRATCH_FLOATS]
     int64_t *tok = nullptr;                      // [max_sessions]
@@ -169,6 +173,7 @@ int dev_alloc(void **p, size_t bytes);
 // helpers shared with tp.hip
 int ensure_pages(vlo_session *s, int64_t new_len, hipStream_t st);
 GemvArgs gemv_args(const PackedLinear &pl, const unsigned short *x, int ldx, int n_rows);
+GemvArgs qkv_args(const vlo_engine *e, int layer, const StepWs &w, int n_rows, int64_t pos0);   // w.x -> w.q; the epilogue comes from rope_epi
 KvPool kv_geom(const vlo_session *s);
 // the qkv projection's append target: sets a.kv (+ a.kv_scale) and returns the epilogue, EPI_ROPE or EPI_ROPE_F8
 inline int rope_epi(GemvArgs &a, const KvPool &kv) {

@@ -72,6 +72,26 @@ int dev_alloc(void **p, size_t bytes) {
     HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
     return VLO_OK;
 }
+// allocate, zero, remember: device memory for *p that is freed with its owner (`owned`).  Chains through rc: nothing happens after an earlier
+// failure, and a buffer that exists (kept from an earlier, partly failed attempt) stays
+template <typename T>
+static void alloc_owned(int &rc, std::vector<void *> &owned, T **p, size_t bytes, bool zero = true) {
+    if (rc || *p) return;
+    void *q = nullptr;
+    if ((rc = dev_alloc(&q, bytes))) return;
+    owned.push_back(q);
+    if (zero) hipMemset(q, 0, bytes);
+    *p = (T *)q;
+}
+// the activations of a StepWs for up to VLO_BLOCK_TOKENS rows (a session's block set, a batch's set)
+static void alloc_block_rows(int &rc, std::vector<void *> &owned, const vlo_engine *e, StepWs &w, bool zero) {
+    const size_t H = e->cfg.hidden_size, I = e->I_l, qd = (size_t)e->nh_l * e->head_dim, R = VLO_BLOCK_TOKENS;
+    alloc_owned(rc, owned, &w.h, R * H * 2, zero);
+    alloc_owned(rc, owned, &w.x, R * H * 2, zero);
+    alloc_owned(rc, owned, &w.q, R * qd * 2, zero);
+    alloc_owned(rc, owned, &w.attn, R * qd * 2, zero);
+    alloc_owned(rc, owned, &w.act, R * I * 2, zero);
+}
 
 // ------------------------------------------------------------------------------------
 // engine
@@ -428,45 +448,38 @@ int vlo_session_create(vlo_engine *e, int64_t max_tokens_hint, vlo_session **out
     if (!e || !out) return fail(VLO_E_INVALID, "null argument");
     if (!e->finalized) return fail(VLO_E_STATE, "engine not finalized");
     HIP_TRY(hipSetDevice(e->device));
-    (void)max_tokens_hint;
+    (void)max_tokens_hint;                      // (ABI: the workspaces do not depend on it)
     const vlo_config &c = e->cfg;
-    const int H = c.hidden_size, I = e->I_l, hd = e->head_dim, nh = e->nh_l, nkv = e->nkv_l;
-    const int Nqkv = (nh + 2 * nkv) * hd;
+    const int H = c.hidden_size, I = e->I_l, hd = e->head_dim, nh = e->nh_l;
     vlo_session *s = new vlo_session();
     s->e = e;
+    StepWs &w = s->ws;
     int rc = 0;
-    auto A = [&](void **p, size_t bytes) {
-        if (rc) return;
-        rc = dev_alloc(p, bytes);
-        if (!rc) {
-            s->owned.push_back(*p);
-            hipMemset(*p, 0, bytes);
-        }
-    };
-    A((void **)&s->h, (size_t)32 * H * 2);
-    A((void **)&s->x, (size_t)32 * H * 2);
-    A((void **)&s->act, (size_t)32 * I * 2);
-    A((void **)&s->attn, (size_t)32 * nh * hd * 2);
-    A((void **)&s->q, (size_t)16 * nh * hd * 2);
-    (void)Nqkv;
+    auto A = [&](auto **p, size_t bytes) { alloc_owned(rc, s->owned, p, bytes); };
+    A(&w.h, (size_t)32 * H * 2);
+    A(&w.x, (size_t)32 * H * 2);
+    A(&w.act, (size_t)32 * I * 2);
+    A(&w.attn, (size_t)32 * nh * hd * 2);
+    A(&w.q, (size_t)16 * nh * hd * 2);
     int ksmax = 1;
     for (auto &L : e->layers) ksmax = std::max(ksmax, L.down.plan.ksplit);
-    A((void **)&s->partial, (size_t)ksmax * 16 * H * 4);
-    A((void **)&s->sq[0], (size_t)(512 + 16) * 16 * 4);      // row sum-of-squares partials: [gemv grid.x <= 512][16] (+ row offset slack)
-    A((void **)&s->sq[1], (size_t)(512 + 16) * 16 * 4);
-    A((void **)&s->part_o, (size_t)VLO_MAX_SPLITS * nh * 16 * hd * 4);
-    A((void **)&s->part_ml, (size_t)VLO_MAX_SPLITS * nh * 16 * 2 * 4);
-    A((void **)&s->logits, (size_t)16 * c.vocab_size * 2);
+    A(&w.partial, (size_t)ksmax * 16 * H * 4);
+    A(&w.sq[0], (size_t)(512 + 16) * 16 * 4);      // row sum-of-squares partials: [gemv grid.x <= 512][16] (+ row offset slack)
+    A(&w.sq[1], (size_t)(512 + 16) * 16 * 4);
+    w.part_cap = VLO_MAX_SPLITS;
+    A(&w.part_o, (size_t)w.part_cap * nh * 16 * hd * 4);
+    A(&w.part_ml, (size_t)w.part_cap * nh * 16 * 2 * 4);
+    A(&s->logits, (size_t)16 * c.vocab_size * 2);
     if (e->tp_size > 1) {
         int ks_o = 1;
         for (auto &L : e->layers) ks_o = std::max(ks_o, L.o.plan.ksplit);
-        A((void **)&s->logits_local, (size_t)16 * e->V_l * 2);
-        A((void **)&s->partial_o, (size_t)ks_o * 16 * H * 4);
+        A(&s->logits_local, (size_t)16 * e->V_l * 2);
+        A(&s->partial_o, (size_t)ks_o * 16 * H * 4);
     }
-    A((void **)&s->tok, 64);
-    A((void **)&s->sample_scratch, VLO_SAMPLE_SCRATCH_FLOATS * 4);
-    A((void **)&s->emb1, (size_t)32 * H * 2);
-    A((void **)&s->page_table, (size_t)e->pool_pages * 4);
+    A(&s->tok, 64);
+    A(&s->sample_scratch, VLO_SAMPLE_SCRATCH_FLOATS * 4);
+    A(&s->emb1, (size_t)32 * H * 2);
+    A(&s->page_table, (size_t)e->pool_pages * 4);
     if (rc) {
         vlo_session_destroy(s);
         return rc;
@@ -640,63 +653,130 @@ GemvArgs gemv_args(const PackedLinear &pl, const unsigned short *x, int ldx, int
     return a;
 }
 
-// one chunk of m <= 16 new tokens whose embeddings are at `src`.  Per decoder layer (7 launches):
+GemvArgs qkv_args(const vlo_engine *e, int layer, const StepWs &w, int n_rows, int64_t pos0) {
+    GemvArgs a = gemv_args(e->layers[layer].qkv, w.x, e->cfg.hidden_size, n_rows);
+    a.out_bf16 = w.q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
+    a.layer = layer; a.num_heads = e->nh_l; a.pos0 = pos0;
+    return a;
+}
+
+// Where the rows of a pass sit in the KV cache: the one thing a solo step and a batched step differ in.
+//   solo    (segs == nullptr): consecutive positions pos0 .. pos0 + M - 1 of one session, whose page table is kv.page_table
+//   batched (segs != nullptr): each row's position and page in the device row table `rows` (EPI_ROPE_ROWS), attention per planned segment
+struct KvRows {
+    KvPool kv;
+    int64_t pos0 = 0;
+    const RopeRow *rows = nullptr;
+    const AttnSeg *segs = nullptr; const AttnSegRun *runs = nullptr; int nseg = 0, nrun = 0;   // device table + its host-side launch plan (attention_seg_plan)
+};
+// the last layer's down-proj partial sums, not yet folded into h: the caller's final add_rmsnorm combines them (16-row pipeline; none on the block path)
+struct PendingDown { const float *partial = nullptr; int ksplit = 0; };
+
+// The decoder layers of one pass over M new rows whose embeddings are in w.h.  Two pipelines over the same packed weights:
+//
+// 16-row (M <= 16; GEMVs, every matrix row-major), 7 launches per layer:
 //   add_rmsnorm   [+ down-proj split-K combine + residual of the previous layer]      -> x
 //   qkv GEMV      [RoPE + paged KV append in the epilogue]                             -> q, K, V^T
 //   attention, combine                                                                 -> attn
 //   o GEMV        [residual add + row sum-of-squares partials in the epilogue]         -> h, sq
 //   gate/up GEMV  [post-attention RMSNorm fused into the operand load | SwiGLU]        -> act
-//   down GEMV     [K split over blocks, fp32 partials]                                 -> partial
-static int run_chunk(vlo_session *s, const unsigned short *src, int m, bool want_last, bool want_all, hipStream_t st) {
-    vlo_engine *e = s->e;
+//   down GEMV     [K split over blocks, fp32 partials]                                 -> partial (left pending for the caller after the last layer)
+//
+// block (16 < M <= 64; gemm64 of prefill.hip, x / attn / act packed-64), 8 launches per layer:
+//   RMSNorm rows -> qkv GEMM [RoPE + KV append] -> attention over the (up to four) 16-query sub-chunks, combine -> o GEMM [residual add]
+//   -> RMSNorm rows -> gate/up GEMM [SwiGLU] -> down GEMM [residual add]
+// Same rounding points as the 16-row pipeline (projection outputs and residual sums are bf16, accumulation fp32); only the fp32 summation
+// order inside a dot product differs (K is split over the waves of a block differently).
+//
+// profile: bracket the gate/up GEMV for vlo_profile_read (solo 16-row steps only).
+static int decoder_layers(vlo_engine *e, const StepWs &w, int M, bool block, const KvRows &at, bool profile, hipStream_t st, PendingDown *pending) {
     const vlo_config &c = e->cfg;
-    const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads;
-    int rc;
-    if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-    const KvPool kv = kv_geom(s);
-    HIP_TRY(copy_rows_launch(src, s->h, m, H, st));
+    const int H = c.hidden_size, I = e->I_l, hd = e->head_dim, nh = e->nh_l;
+    const int ldx = block ? 0 : H;                     // 0: packed-64
+    const bool batched = at.segs != nullptr;
+    KvPool kv_append = at.kv;
+    if (batched) kv_append.page_table = reinterpret_cast<const int *>(at.rows);   // EPI_ROPE_ROWS reads the row table through kv.page_table (gemv.h)
     const float *prev = nullptr;
     int prev_ks = 0;
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerWeights &L = e->layers[l];
-        HIP_TRY(add_rmsnorm_launch(s->h, prev, prev_ks, H, (const unsigned short *)L.ln_in, s->x, H, H, c.rms_eps, m, st));
-        {   // qkv
-            GemvArgs a = gemv_args(L.qkv, s->x, H, m);
-            a.out_bf16 = s->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.layer = l; a.num_heads = nh; a.pos0 = s->len;
-            const int epi = rope_epi(a, kv);
-            HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
+        HIP_TRY(add_rmsnorm_launch(w.h, prev, prev_ks, H, (const unsigned short *)L.ln_in, w.x, H, ldx, c.rms_eps, M, st));
+        {   // qkv [RoPE + KV append: at pos0 + row, or at each row's own position and page]
+            GemvArgs a = qkv_args(e, l, w, M, at.pos0);
+            int epi = rope_epi(a, kv_append);
+            if (batched) epi = epi == EPI_ROPE_F8 ? EPI_ROPE_ROWS_F8 : EPI_ROPE_ROWS;
+            if (block) HIP_TRY(gemm64_launch(a, L.qkv.plan64, epi, st));
+            else HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
         }
-        HIP_TRY(attention_launch(s->q, kv, l, nh, s->len, m, s->part_o, s->part_ml, s->attn, st));
-        int sq_parts;
+        // one launch for the (up to four) 16-query sub-chunks of a block; its keys are already appended
+        if (batched) HIP_TRY(attention_seg_launch(w.q, at.kv, l, nh, at.segs, at.nseg, at.runs, at.nrun, w.part_o, w.part_ml, w.attn, block, st));
+        else HIP_TRY(attention_launch(w.q, at.kv, l, nh, at.pos0, M, w.part_o, w.part_ml, w.attn, st, block ? 0 : -1, w.part_cap));
+        int sq_parts = 0;
         {   // o_proj + residual
-            GemvArgs a = gemv_args(L.o, s->attn, nh * hd, m);
-            a.h = s->h; a.ldo = H; a.sq_out = s->sq[0];
-            sq_parts = gemv_grid_x(a, L.o.plan, EPI_RESID);
-            HIP_TRY(gemv_launch(a, L.o.plan, XSRC_PLAIN, EPI_RESID, st));
+            GemvArgs a = gemv_args(L.o, w.attn, nh * hd, M);
+            a.h = w.h; a.ldo = H;
+            if (block) {
+                HIP_TRY(gemm64_launch(a, L.o.plan64, EPI_RESID, st));
+            } else {
+                a.sq_out = w.sq[0];
+                sq_parts = gemv_grid_x(a, L.o.plan, EPI_RESID);
+                HIP_TRY(gemv_launch(a, L.o.plan, XSRC_PLAIN, EPI_RESID, st));
+            }
+        }
+        if (block) {
+            HIP_TRY(add_rmsnorm_launch(w.h, nullptr, 0, H, (const unsigned short *)L.ln_post, w.x, H, 0, c.rms_eps, M, st));
+            GemvArgs a = gemv_args(L.gate_up, w.x, H, M);              // gate/up + SwiGLU
+            a.out_bf16 = w.act; a.ldo = I;
+            HIP_TRY(gemm64_launch(a, L.gate_up.plan64, EPI_SWIGLU, st));
+            GemvArgs d = gemv_args(L.down, w.act, I, M);               // down_proj + residual
+            d.h = w.h; d.ldo = H;
+            HIP_TRY(gemm64_launch(d, L.down.plan64, EPI_RESID, st));
+            continue;
         }
         {   // gate/up + SwiGLU
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (e->prof_stride > 0 && (e->prof_seen++ % e->prof_stride) == 0) prof_acquire(e, &ev0, &ev1);
-            GemvArgs a = gemv_args(L.gate_up, s->h, H, m);
-            a.norm_w = (const unsigned short *)L.ln_post; a.sq_in = s->sq[0]; a.sq_in_parts = sq_parts; a.eps = c.rms_eps;
-            a.out_bf16 = s->act; a.ldo = I;
+            if (profile && e->prof_stride > 0 && (e->prof_seen++ % e->prof_stride) == 0) prof_acquire(e, &ev0, &ev1);
+            GemvArgs a = gemv_args(L.gate_up, w.h, H, M);
+            a.norm_w = (const unsigned short *)L.ln_post; a.sq_in = w.sq[0]; a.sq_in_parts = sq_parts; a.eps = c.rms_eps;
+            a.out_bf16 = w.act; a.ldo = I;
             if (ev0) hipEventRecord(ev0, st);
             HIP_TRY(gemv_launch(a, L.gate_up.plan, XSRC_NORM, EPI_SWIGLU, st));
             if (ev1) hipEventRecord(ev1, st);
         }
         {   // down_proj: fp32 K-slice partials, combined by the next add_rmsnorm
-            GemvArgs a = gemv_args(L.down, s->act, I, m);
-            a.out_f32 = s->partial; a.ldo = H;
+            GemvArgs a = gemv_args(L.down, w.act, I, M);
+            a.out_f32 = w.partial; a.ldo = H;
             HIP_TRY(gemv_launch(a, L.down.plan, XSRC_PLAIN, EPI_PARTIAL_F32, st));
-            prev = s->partial;
+            prev = w.partial;
             prev_ks = L.down.plan.ksplit;
         }
     }
+    pending->partial = prev;
+    pending->ksplit = prev_ks;
+    return VLO_OK;
+}
+
+static KvRows solo_rows(const vlo_session *s) {   // a solo step's rows: consecutive positions behind the session's cache
+    KvRows at;
+    at.kv = kv_geom(s); at.pos0 = s->len;
+    return at;
+}
+
+// one chunk of m <= 16 new tokens whose embeddings are at `src`: the 16-row pipeline
+static int run_chunk(vlo_session *s, const unsigned short *src, int m, bool want_last, bool want_all, hipStream_t st) {
+    vlo_engine *e = s->e;
+    const vlo_config &c = e->cfg;
+    const StepWs &w = s->ws;
+    const int H = c.hidden_size;
+    int rc;
+    if ((rc = ensure_pages(s, s->len + m, st))) return rc;
+    HIP_TRY(copy_rows_launch(src, w.h, m, H, st));
+    PendingDown pd;
+    if ((rc = decoder_layers(e, w, m, false, solo_rows(s), true, st, &pd))) return rc;
     if (want_last || want_all) {
-        HIP_TRY(add_rmsnorm_launch(s->h, prev, prev_ks, H, (const unsigned short *)e->norm_w, s->x, H, H, c.rms_eps, m, st));
+        HIP_TRY(add_rmsnorm_launch(w.h, pd.partial, pd.ksplit, H, (const unsigned short *)e->norm_w, w.x, H, H, c.rms_eps, m, st));
         const int r0 = want_all ? 0 : m - 1, nr = want_all ? m : 1;        // only the rows that are read
-        GemvArgs a = gemv_args(e->lm_head, s->x + (size_t)r0 * H, H, nr);
+        GemvArgs a = gemv_args(e->lm_head, w.x + (size_t)r0 * H, H, nr);
         a.out_bf16 = s->logits; a.ldo = c.vocab_size;
         HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
         s->last_logits = s->logits + (size_t)(nr - 1) * c.vocab_size;
@@ -708,78 +788,52 @@ static int run_chunk(vlo_session *s, const unsigned short *src, int m, bool want
 
 // ---- block path: up to 64 new tokens per weight pass (prefill.hip) ---------------------------------------------------
 static int ensure_block_ws(vlo_session *s) {
-    if (s->bact) return VLO_OK;                 // the LAST buffer allocated below: set only when all of them exist
-    vlo_engine *e = s->e;
-    const size_t H = e->cfg.hidden_size, I = e->I_l, qd = (size_t)e->nh_l * e->head_dim, R = VLO_BLOCK_TOKENS;
-    struct { unsigned short **p; size_t elems; } want[] = {{&s->bh, R * H}, {&s->bx, R * H}, {&s->bq, R * qd}, {&s->battn, R * qd}, {&s->bact, R * I}};
-    HIP_TRY(hipSetDevice(e->device));
-    for (auto &w : want) {
-        if (*w.p) continue;                     // kept from an earlier, partially failed attempt
-        void *p = nullptr;
-        int rc = dev_alloc(&p, w.elems * 2);
-        if (rc) return rc;
-        s->owned.push_back(p);
-        *w.p = (unsigned short *)p;
+    StepWs &w = s->bws;
+    if (w.act) return VLO_OK;                   // the LAST buffer allocated below: set only when all of them exist
+    HIP_TRY(hipSetDevice(s->e->device));
+    int rc = 0;
+    alloc_block_rows(rc, s->owned, s->e, w, false);
+    w.part_o = s->ws.part_o; w.part_ml = s->ws.part_ml; w.part_cap = s->ws.part_cap;   // one pass at a time per session: shared with the 16-row set
+    return rc;
+}
+
+// The end of a block / prefill pass that was asked for logits: the session keeps the last row's.  all_logits: the caller's matrix, every row
+// already written by the pass — the last row is copied out of it; else row m - 1 of x (the final-normed rows, row-major) goes through the GEMV.
+static int last_row_logits(vlo_session *s, const unsigned short *x, int m, const unsigned short *all_logits, hipStream_t st) {
+    const vlo_engine *e = s->e;
+    const int H = e->cfg.hidden_size, V = e->cfg.vocab_size;
+    if (all_logits) {
+        HIP_TRY(hipMemcpyAsync(s->logits, all_logits + (size_t)(m - 1) * V, (size_t)V * 2, hipMemcpyDeviceToDevice, st));
+    } else {                                    // only the row that is read
+        GemvArgs a = gemv_args(e->lm_head, x + (size_t)(m - 1) * H, H, 1);
+        a.out_bf16 = s->logits; a.ldo = V;
+        HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
     }
+    s->last_logits = s->logits;
+    s->has_logits = true;
     return VLO_OK;
 }
 
-// one block of 16 < m <= 64 new tokens.  Per decoder layer: RMSNorm rows -> qkv GEMM [RoPE + KV append] -> attention per
-// 16-query sub-chunk (+ combine) -> o GEMM [residual add] -> RMSNorm rows -> gate/up GEMM [SwiGLU] -> down GEMM [residual
-// add].  Same rounding points as run_chunk (projection outputs and residual sums are bf16, accumulation fp32); only the
-// fp32 summation order inside a dot product differs (K is split over the waves of a block differently).
+// one block of 16 < m <= 64 new tokens: the block pipeline
 static int run_block(vlo_session *s, const unsigned short *src, int m, bool want_last, unsigned short *all_logits, hipStream_t st) {
     vlo_engine *e = s->e;
     const vlo_config &c = e->cfg;
-    const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads, V = c.vocab_size;
+    const StepWs &w = s->bws;
+    const int H = c.hidden_size, V = c.vocab_size;
     int rc;
     if ((rc = ensure_block_ws(s))) return rc;
     if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-    const KvPool kv = kv_geom(s);
-    HIP_TRY(copy_rows_launch(src, s->bh, m, H, st));
-    for (int l = 0; l < c.num_layers; ++l) {
-        const LayerWeights &L = e->layers[l];
-        HIP_TRY(add_rmsnorm_launch(s->bh, nullptr, 0, H, (const unsigned short *)L.ln_in, s->bx, H, 0, c.rms_eps, m, st));   // packed-64
-        {   // qkv
-            GemvArgs a = gemv_args(L.qkv, s->bx, H, m);
-            a.out_bf16 = s->bq; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.layer = l; a.num_heads = nh; a.pos0 = s->len;
-            const int epi = rope_epi(a, kv);
-            HIP_TRY(gemm64_launch(a, L.qkv.plan64, epi, st));
-        }
-        // one launch for the (up to four) 16-query sub-chunks; the keys of the whole block are already appended
-        HIP_TRY(attention_launch(s->bq, kv, l, nh, s->len, m, s->part_o, s->part_ml, s->battn, st, 0));
-        {   // o_proj + residual
-            GemvArgs a = gemv_args(L.o, s->battn, nh * hd, m);
-            a.h = s->bh; a.ldo = H;
-            HIP_TRY(gemm64_launch(a, L.o.plan64, EPI_RESID, st));
-        }
-        HIP_TRY(add_rmsnorm_launch(s->bh, nullptr, 0, H, (const unsigned short *)L.ln_post, s->bx, H, 0, c.rms_eps, m, st));
-        {   // gate/up + SwiGLU
-            GemvArgs a = gemv_args(L.gate_up, s->bx, H, m);
-            a.out_bf16 = s->bact; a.ldo = I;
-            HIP_TRY(gemm64_launch(a, L.gate_up.plan64, EPI_SWIGLU, st));
-        }
-        {   // down_proj + residual
-            GemvArgs a = gemv_args(L.down, s->bact, I, m);
-            a.h = s->bh; a.ldo = H;
-            HIP_TRY(gemm64_launch(a, L.down.plan64, EPI_RESID, st));
-        }
-    }
+    HIP_TRY(copy_rows_launch(src, w.h, m, H, st));
+    PendingDown pd;                             // (nothing pending on the block path: its down GEMM adds into h)
+    if ((rc = decoder_layers(e, w, m, true, solo_rows(s), false, st, &pd))) return rc;
     if (want_last || all_logits) {
-        HIP_TRY(add_rmsnorm_launch(s->bh, nullptr, 0, H, (const unsigned short *)e->norm_w, s->bx, H, all_logits ? 0 : H, c.rms_eps, m, st));
+        HIP_TRY(add_rmsnorm_launch(w.h, nullptr, 0, H, (const unsigned short *)e->norm_w, w.x, H, all_logits ? 0 : H, c.rms_eps, m, st));
         if (all_logits) {                       // every row, straight into the caller's matrix
-            GemvArgs a = gemv_args(e->lm_head, s->bx, H, m);
+            GemvArgs a = gemv_args(e->lm_head, w.x, H, m);
             a.out_bf16 = all_logits; a.ldo = V;
             HIP_TRY(gemm64_launch(a, e->lm_head.plan64, EPI_BF16, st));
-            HIP_TRY(hipMemcpyAsync(s->logits, all_logits + (size_t)(m - 1) * V, (size_t)V * 2, hipMemcpyDeviceToDevice, st));
-        } else {                                // only the row that is read
-            GemvArgs a = gemv_args(e->lm_head, s->bx + (size_t)(m - 1) * H, H, 1);
-            a.out_bf16 = s->logits; a.ldo = V;
-            HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
         }
-        s->last_logits = s->logits;
-        s->has_logits = true;
+        if ((rc = last_row_logits(s, w.x, m, all_logits, st))) return rc;
     }
     s->len += m;
     return VLO_OK;
@@ -906,7 +960,7 @@ int prefill_gemm(vlo_session *s, const unsigned short *X, const PackedLinear &pl
 static int run_prefill(vlo_session *s, const unsigned short *src, int m, bool want_last, unsigned short *all_logits, hipStream_t st) {
     vlo_engine *e = s->e;
     const vlo_config &c = e->cfg;
-    const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads, nkv = c.num_kv_heads, V = c.vocab_size;
+    const int H = c.hidden_size, I = e->I_l, hd = e->head_dim, nh = e->nh_l, nkv = e->nkv_l, V = c.vocab_size;
     const int qd = nh * hd, Nqkv = qd + 2 * nkv * hd;
     int rc;
     if ((rc = ensure_prefill_ws(s))) return rc;
@@ -946,14 +1000,8 @@ static int run_prefill(vlo_session *s, const unsigned short *src, int m, bool wa
                     HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
                 }
             }
-            HIP_TRY(hipMemcpyAsync(s->logits, all_logits + (size_t)(m - 1) * V, (size_t)V * 2, hipMemcpyDeviceToDevice, st));
-        } else {                                // only the row that is read
-            GemvArgs a = gemv_args(e->lm_head, s->px + (size_t)(m - 1) * H, H, 1);
-            a.out_bf16 = s->logits; a.ldo = V;
-            HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
         }
-        s->last_logits = s->logits;
-        s->has_logits = true;
+        if ((rc = last_row_logits(s, s->px, m, all_logits, st))) return rc;
     }
     s->len += m;
     return VLO_OK;
@@ -1117,38 +1165,28 @@ int vlo_batch_create(vlo_engine *e, int max_sessions, vlo_batch **out) {
     const vlo_config &c = e->cfg;
     if (c.vocab_size & 7) return fail(VLO_E_UNSUPPORTED, "batched steps need vocab_size % 8 == 0");
     HIP_TRY(hipSetDevice(e->device));
-    const size_t H = c.hidden_size, I = e->I_l, hd = e->head_dim, qd = (size_t)e->nh_l * hd, V = c.vocab_size, R = VLO_BLOCK_TOKENS;
+    const size_t H = c.hidden_size, hd = e->head_dim, V = c.vocab_size;
     vlo_batch *b = new vlo_batch();
     b->e = e;
     b->max_sessions = max_sessions;
+    StepWs &w = b->ws;
     int ksmax = 1;
     for (auto &L : e->layers) ksmax = std::max(ksmax, L.down.plan.ksplit);
-    b->part_cap = max_sessions * attention_states_bound(e->nkv_l);
+    w.part_cap = max_sessions * attention_states_bound(e->nkv_l);
     int rc = 0;
-    auto A = [&](void **p, size_t bytes) {
-        if (rc) return;
-        rc = dev_alloc(p, bytes);
-        if (!rc) {
-            b->owned.push_back(*p);
-            hipMemset(*p, 0, bytes);
-        }
-    };
-    A((void **)&b->h, R * H * 2);
-    A((void **)&b->x, R * H * 2);
-    A((void **)&b->q, R * qd * 2);
-    A((void **)&b->attn, R * qd * 2);
-    A((void **)&b->act, R * I * 2);
-    A((void **)&b->xl, (size_t)16 * H * 2);
-    A((void **)&b->emb, (size_t)16 * H * 2);
-    A((void **)&b->partial, (size_t)ksmax * 16 * H * 4);
-    A((void **)&b->sq[0], (size_t)(512 + 16) * 16 * 4);
-    A((void **)&b->sq[1], (size_t)(512 + 16) * 16 * 4);
-    A((void **)&b->part_o, (size_t)b->part_cap * e->nh_l * 16 * hd * 4);
-    A((void **)&b->part_ml, (size_t)b->part_cap * e->nh_l * 16 * 2 * 4);
-    A((void **)&b->logits, (size_t)max_sessions * V * 2);
-    A((void **)&b->sample_scratch, (size_t)max_sessions * VLO_SAMPLE_SCRATCH_FLOATS * 4);
-    A((void **)&b->tok, (size_t)max_sessions * 8);
-    A((void **)&b->tables_dev, sizeof(BatchTables) * VLO_BATCH_SLOTS);
+    auto A = [&](auto **p, size_t bytes) { alloc_owned(rc, b->owned, p, bytes); };
+    alloc_block_rows(rc, b->owned, e, w, true);
+    A(&b->xl, (size_t)16 * H * 2);
+    A(&b->emb, (size_t)16 * H * 2);
+    A(&w.partial, (size_t)ksmax * 16 * H * 4);
+    A(&w.sq[0], (size_t)(512 + 16) * 16 * 4);
+    A(&w.sq[1], (size_t)(512 + 16) * 16 * 4);
+    A(&w.part_o, (size_t)w.part_cap * e->nh_l * 16 * hd * 4);
+    A(&w.part_ml, (size_t)w.part_cap * e->nh_l * 16 * 2 * 4);
+    A(&b->logits, (size_t)max_sessions * V * 2);
+    A(&b->sample_scratch, (size_t)max_sessions * VLO_SAMPLE_SCRATCH_FLOATS * 4);
+    A(&b->tok, (size_t)max_sessions * 8);
+    A(&b->tables_dev, sizeof(BatchTables) * VLO_BATCH_SLOTS);
     if (rc) {
         vlo_batch_destroy(b);
         return rc;
@@ -1234,7 +1272,8 @@ int vlo_batch_step(vlo_batch *b, vlo_session *const *ss, int B, const void *embe
     if (M > VLO_BLOCK_TOKENS) return fail(VLO_E_INVALID, "batch of " + std::to_string(M) + " rows: at most " + std::to_string(VLO_BLOCK_TOKENS) + " (split the batch)");
     vlo_engine *e = b->e;
     const vlo_config &c = e->cfg;
-    const int H = c.hidden_size, I = c.intermediate_size, hd = e->head_dim, nh = c.num_heads, V = c.vocab_size;
+    const StepWs &w = b->ws;
+    const int H = c.hidden_size, V = c.vocab_size;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
     if ((rc = batch_pages(ss, B, n_host, st))) return rc;
@@ -1257,77 +1296,24 @@ int vlo_batch_step(vlo_batch *b, vlo_session *const *ss, int B, const void *embe
             T.rows[r].page = s->pages[pos / VLO_PAGE_TOKENS];
         }
     }
-    const KvPool kv = kv_geom(ss[0]);                  // pool geometry (each segment / row carries its own pages)
-    AttnSegRun runs[4];
-    int nseg = 0, nrun = 0, states = 0;
-    HIP_TRY(attention_seg_plan(kv, nh, B, tables, lens, n_host, rows, b->part_cap, T.segs, &nseg, runs, &nrun, &states));
     BatchTables *Td = b->tables_dev + k;
+    AttnSegRun runs[4];
+    KvRows at;
+    at.kv = kv_geom(ss[0]);                            // pool geometry (each segment / row carries its own pages)
+    at.rows = Td->rows; at.segs = Td->segs; at.runs = runs;
+    int states = 0;
+    HIP_TRY(attention_seg_plan(at.kv, e->nh_l, B, tables, lens, n_host, rows, w.part_cap, T.segs, &at.nseg, runs, &at.nrun, &states));
     HIP_TRY(hipMemcpyAsync(Td, &T, sizeof(BatchTables), hipMemcpyHostToDevice, st));
-    KvPool kvr = kv;
-    kvr.page_table = reinterpret_cast<const int *>(Td->rows);   // EPI_ROPE_ROWS reads the row table through kv.page_table (gemv.h)
 
-    // ---- the decoder layers: run_chunk's sequence (M <= 16) or run_block's (17..64 rows)
-    const bool block = M > 16;
-    HIP_TRY(copy_rows_launch((const unsigned short *)embeds_dev, b->h, M, H, st));
-    const float *prev = nullptr;
-    int prev_ks = 0;
-    for (int l = 0; l < c.num_layers; ++l) {
-        const LayerWeights &L = e->layers[l];
-        HIP_TRY(add_rmsnorm_launch(b->h, prev, prev_ks, H, (const unsigned short *)L.ln_in, b->x, H, block ? 0 : H, c.rms_eps, M, st));
-        {   // qkv [RoPE + KV append at each row's own position and page]
-            GemvArgs a = gemv_args(L.qkv, b->x, H, M);
-            a.out_bf16 = b->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.layer = l; a.num_heads = nh; a.pos0 = 0;
-            const int epi = rope_epi(a, kvr) == EPI_ROPE_F8 ? EPI_ROPE_ROWS_F8 : EPI_ROPE_ROWS;
-            if (block) HIP_TRY(gemm64_launch(a, L.qkv.plan64, epi, st));
-            else HIP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
-        }
-        HIP_TRY(attention_seg_launch(b->q, kv, l, nh, Td->segs, nseg, runs, nrun, b->part_o, b->part_ml, b->attn, block, st));
-        if (block) {
-            {   // o_proj + residual
-                GemvArgs a = gemv_args(L.o, b->attn, nh * hd, M);
-                a.h = b->h; a.ldo = H;
-                HIP_TRY(gemm64_launch(a, L.o.plan64, EPI_RESID, st));
-            }
-            HIP_TRY(add_rmsnorm_launch(b->h, nullptr, 0, H, (const unsigned short *)L.ln_post, b->x, H, 0, c.rms_eps, M, st));
-            {   // gate/up + SwiGLU
-                GemvArgs a = gemv_args(L.gate_up, b->x, H, M);
-                a.out_bf16 = b->act; a.ldo = I;
-                HIP_TRY(gemm64_launch(a, L.gate_up.plan64, EPI_SWIGLU, st));
-            }
-            {   // down_proj + residual
-                GemvArgs a = gemv_args(L.down, b->act, I, M);
-                a.h = b->h; a.ldo = H;
-                HIP_TRY(gemm64_launch(a, L.down.plan64, EPI_RESID, st));
-            }
-            continue;
-        }
-        int sq_parts;
-        {   // o_proj + residual
-            GemvArgs a = gemv_args(L.o, b->attn, nh * hd, M);
-            a.h = b->h; a.ldo = H; a.sq_out = b->sq[0];
-            sq_parts = gemv_grid_x(a, L.o.plan, EPI_RESID);
-            HIP_TRY(gemv_launch(a, L.o.plan, XSRC_PLAIN, EPI_RESID, st));
-        }
-        {   // gate/up + SwiGLU
-            GemvArgs a = gemv_args(L.gate_up, b->h, H, M);
-            a.norm_w = (const unsigned short *)L.ln_post; a.sq_in = b->sq[0]; a.sq_in_parts = sq_parts; a.eps = c.rms_eps;
-            a.out_bf16 = b->act; a.ldo = I;
-            HIP_TRY(gemv_launch(a, L.gate_up.plan, XSRC_NORM, EPI_SWIGLU, st));
-        }
-        {   // down_proj: fp32 K-slice partials, combined by the next add_rmsnorm
-            GemvArgs a = gemv_args(L.down, b->act, I, M);
-            a.out_f32 = b->partial; a.ldo = H;
-            HIP_TRY(gemv_launch(a, L.down.plan, XSRC_PLAIN, EPI_PARTIAL_F32, st));
-            prev = b->partial;
-            prev_ks = L.down.plan.ksplit;
-        }
-    }
+    // ---- the decoder layers: the 16-row pipeline (M <= 16) or the block pipeline (17..64 rows)
+    HIP_TRY(copy_rows_launch((const unsigned short *)embeds_dev, w.h, M, H, st));
+    PendingDown pd;
+    if ((rc = decoder_layers(e, w, M, M > 16, at, false, st, &pd))) return rc;
     // ---- each session's last row: final norm, gathered into B rows, one lm_head pass, scattered to the sessions
-    HIP_TRY(add_rmsnorm_launch(b->h, prev, prev_ks, H, (const unsigned short *)e->norm_w, b->x, H, H, c.rms_eps, M, st));
+    HIP_TRY(add_rmsnorm_launch(w.h, pd.partial, pd.ksplit, H, (const unsigned short *)e->norm_w, w.x, H, H, c.rms_eps, M, st));
     RowCopy g{}, sc{};
     for (int i = 0; i < B; ++i) {
-        g.src[i] = b->x + (size_t)(rows[i] + n_host[i] - 1) * H;
+        g.src[i] = w.x + (size_t)(rows[i] + n_host[i] - 1) * H;
         g.dst[i] = b->xl + (size_t)i * H;
         sc.src[i] = b->logits + (size_t)i * V;
         sc.dst[i] = ss[i]->logits;
@@ -1778,7 +1764,8 @@ int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, doubl
 
 int vlo_debug_read(vlo_session *s, int which, void *dst_dev, int64_t bytes, void *stream) {
     if (!s || !dst_dev || bytes <= 0) return fail(VLO_E_INVALID, "bad debug_read arguments");
-    const void *src = which == 0 ? (void *)s->q : which == 1 ? (void *)s->attn : which == 2 ? (void *)s->h : which == 3 ? (void *)s->act : (void *)s->x;
+    const StepWs &w = s->ws;
+    const void *src = which == 0 ? (void *)w.q : which == 1 ? (void *)w.attn : which == 2 ? (void *)w.h : which == 3 ? (void *)w.act : (void *)w.x;
     HIP_TRY(hipMemcpyAsync(dst_dev, src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return VLO_OK;
 }

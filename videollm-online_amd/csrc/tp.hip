@@ -511,18 +511,22 @@ static P2PPeers p2p_peers(const P2PState &P, int local_idx, int T) {
 }
 
 // ---- exchanges -------------------------------------------------------------------------------------------------
-static int tp_allreduce(vlo_tp_session *t, float *(vlo_session::*buf), size_t count, hipStream_t st) {
+// the buffer of a rank's partial sums that an exchange reduces: the o-proj's or the down-proj's
+static float *partial_o(vlo_session *s) { return s->partial_o; }
+static float *partial_down(vlo_session *s) { return s->ws.partial; }
+
+static int tp_allreduce(vlo_tp_session *t, float *(*buf)(vlo_session *), size_t count, hipStream_t st) {
     vlo_tp_group *g = t->g;
     if (g->tp_size == 1) return VLO_OK;
     if (g->comm) {
-        float *b = t->ss[0]->*buf;
+        float *b = buf(t->ss[0]);
         const int nrc = g_rccl.AllReduce(b, b, count, kNcclFloat32, kNcclSum, g->comm, st);
         if (nrc != 0) return vlo_fail(VLO_E_HIP, rccl_err("ncclAllReduce", nrc));
         return VLO_OK;
     }
     PtrList L;
     L.n = (int)t->ss.size();
-    for (int r = 0; r < L.n; ++r) L.p[r] = t->ss[r]->*buf;
+    for (int r = 0; r < L.n; ++r) L.p[r] = buf(t->ss[r]);
     int blocks = (int)((count + 255) / 256);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(tp_sum_kernel, dim3(blocks), dim3(256), 0, st, L, count);
@@ -551,7 +555,7 @@ static void p2p_publish_args(const vlo_tp_group *g, int local_idx, const XchgId 
 }
 
 // `published`: the partial sums are already in the mailboxes (the GEMVs' epilogues wrote them under *published): collect only
-static int tp_reduce_norm(vlo_tp_session *t, float *(vlo_session::*buf), int ks, int m, const void *(*norm_w)(const vlo_engine *, int), int layer,
+static int tp_reduce_norm(vlo_tp_session *t, float *(*buf)(vlo_session *), int ks, int m, const void *(*norm_w)(const vlo_engine *, int), int layer,
                           hipStream_t st, const XchgId *published = nullptr) {
     vlo_tp_group *g = t->g;
     const int R = (int)t->ss.size();
@@ -563,7 +567,7 @@ static int tp_reduce_norm(vlo_tp_session *t, float *(vlo_session::*buf), int ks,
         if (rc) return rc;
         for (int r = 0; r < R; ++r) {
             vlo_session *s = t->ss[r];
-            TP_TRY(add_rmsnorm_launch(s->h, s->*buf, ks, H, (const unsigned short *)norm_w(s->e, layer), s->x, H, H, c.rms_eps, m, st));
+            TP_TRY(add_rmsnorm_launch(s->ws.h, buf(s), ks, H, (const unsigned short *)norm_w(s->e, layer), s->ws.x, H, H, c.rms_eps, m, st));
         }
         return VLO_OK;
     }
@@ -577,9 +581,9 @@ static int tp_reduce_norm(vlo_tp_session *t, float *(vlo_session::*buf), int ks,
     for (int pass = 0; pass < passes; ++pass)
         for (int r = 0; r < R; ++r) {
             vlo_session *s = t->ss[r];
-            a.partial = s->*buf; a.peers = p2p_peers(P, r, g->tp_size); a.me = s->e->tp_rank;
+            a.partial = buf(s); a.peers = p2p_peers(P, r, g->tp_size); a.me = s->e->tp_rank;
             a.mode = published ? 2 : (P.fused ? 3 : (pass == 0 ? 1 : 2));
-            a.h = s->h; a.w = (const unsigned short *)norm_w(s->e, layer); a.x = s->x; a.err_dev = P.err_dev[r];
+            a.h = s->ws.h; a.w = (const unsigned short *)norm_w(s->e, layer); a.x = s->ws.x; a.err_dev = P.err_dev[r];
             hipLaunchKernelGGL(tp_xchg_norm_kernel, dim3(m), dim3(XCHG_THREADS), 0, st, a);
             TP_TRY(hipGetLastError());
         }
@@ -643,7 +647,7 @@ static int tp_chunk(vlo_tp_session *t, const unsigned short *src, int m, bool wa
     for (int r = 0; r < R; ++r) {
         vlo_session *s = t->ss[r];
         if ((rc = ensure_pages(s, s->len + m, st))) return rc;
-        TP_TRY(copy_rows_launch(src, s->h, m, H, st));
+        TP_TRY(copy_rows_launch(src, s->ws.h, m, H, st));
     }
     int ks_d = 1;
     bool pub_o = false, pub_d = false;          // this exchange's sums were published by the GEMV epilogues (p2p_direct)
@@ -656,14 +660,12 @@ static int tp_chunk(vlo_tp_session *t, const unsigned short *src, int m, bool wa
             const LayerWeights &L = e->layers[l];
             const KvPool kv = kv_geom(s);
             if (l == 0)                         // later layers: x comes out of the reduce + norm that closed the previous layer
-                TP_TRY(add_rmsnorm_launch(s->h, nullptr, 0, H, (const unsigned short *)L.ln_in, s->x, H, H, c.rms_eps, m, st));
-            GemvArgs a = gemv_args(L.qkv, s->x, H, m);
-            a.out_bf16 = s->q; a.cos_tab = (const unsigned short *)e->cos_tab; a.sin_tab = (const unsigned short *)e->sin_tab;
-            a.layer = l; a.num_heads = e->nh_l; a.pos0 = s->len;
+                TP_TRY(add_rmsnorm_launch(s->ws.h, nullptr, 0, H, (const unsigned short *)L.ln_in, s->ws.x, H, H, c.rms_eps, m, st));
+            GemvArgs a = qkv_args(e, l, s->ws, m, s->len);
             const int epi = rope_epi(a, kv);
             TP_TRY(gemv_launch(a, L.qkv.plan, XSRC_PLAIN, epi, st));
-            TP_TRY(attention_launch(s->q, kv, l, e->nh_l, s->len, m, s->part_o, s->part_ml, s->attn, st));
-            GemvArgs o = gemv_args(L.o, s->attn, e->nh_l * hd, m);
+            TP_TRY(attention_launch(s->ws.q, kv, l, e->nh_l, s->len, m, s->ws.part_o, s->ws.part_ml, s->ws.attn, st));
+            GemvArgs o = gemv_args(L.o, s->ws.attn, e->nh_l * hd, m);
             if (r == 0 && (pub_o = p2p_direct(g, L.o.plan))) xo = p2p_begin_reduce(g);
             if (pub_o) {                        // the sums leave the epilogue as granules in every rank's mailbox
                 p2p_publish_args(g, r, xo, &o);
@@ -675,15 +677,15 @@ static int tp_chunk(vlo_tp_session *t, const unsigned short *src, int m, bool wa
             ks_o = L.o.plan.ksplit;
         }
         // exchange 1: h += all-reduce(o_proj partials); x = post-attention RMSNorm(h)
-        if ((rc = tp_reduce_norm(t, &vlo_session::partial_o, ks_o, m, norm_post, l, st, pub_o ? &xo : nullptr))) return rc;
+        if ((rc = tp_reduce_norm(t, partial_o, ks_o, m, norm_post, l, st, pub_o ? &xo : nullptr))) return rc;
         for (int r = 0; r < R; ++r) {           // MLP half
             vlo_session *s = t->ss[r];
             vlo_engine *e = s->e;
             const LayerWeights &L = e->layers[l];
-            GemvArgs a = gemv_args(L.gate_up, s->x, H, m);
-            a.out_bf16 = s->act; a.ldo = e->I_l;
+            GemvArgs a = gemv_args(L.gate_up, s->ws.x, H, m);
+            a.out_bf16 = s->ws.act; a.ldo = e->I_l;
             TP_TRY(gemv_launch(a, L.gate_up.plan, XSRC_PLAIN, EPI_SWIGLU, st));
-            GemvArgs d = gemv_args(L.down, s->act, e->I_l, m);
+            GemvArgs d = gemv_args(L.down, s->ws.act, e->I_l, m);
             // (the last layer's sums are only exchanged when logits are wanted: nothing is published that nobody collects)
             const bool exchanged = l + 1 < c.num_layers || want_last || want_all;
             if (r == 0 && (pub_d = exchanged && p2p_direct(g, L.down.plan))) xd = p2p_begin_reduce(g);
@@ -691,22 +693,22 @@ static int tp_chunk(vlo_tp_session *t, const unsigned short *src, int m, bool wa
                 p2p_publish_args(g, r, xd, &d);
                 TP_TRY(gemv_launch(d, L.down.plan, XSRC_PLAIN, EPI_PARTIAL_MBOX, st));
             } else {
-                d.out_f32 = s->partial; d.ldo = H;
+                d.out_f32 = s->ws.partial; d.ldo = H;
                 TP_TRY(gemv_launch(d, L.down.plan, XSRC_PLAIN, EPI_PARTIAL_F32, st));
             }
             ks_d = L.down.plan.ksplit;
         }
         // exchange 2: h += all-reduce(down_proj partials); x = the next layer's input RMSNorm(h).  After the last layer it
         // is the final norm, and only when logits are wanted (h is not read again otherwise).
-        if (l + 1 < c.num_layers && (rc = tp_reduce_norm(t, &vlo_session::partial, ks_d, m, norm_in, l + 1, st, pub_d ? &xd : nullptr))) return rc;
+        if (l + 1 < c.num_layers && (rc = tp_reduce_norm(t, partial_down, ks_d, m, norm_in, l + 1, st, pub_d ? &xd : nullptr))) return rc;
     }
     if (want_last || want_all) {
         const int r0 = want_all ? 0 : m - 1, nr = want_all ? m : 1;
-        if ((rc = tp_reduce_norm(t, &vlo_session::partial, ks_d, m, norm_final, 0, st, pub_d ? &xd : nullptr))) return rc;
+        if ((rc = tp_reduce_norm(t, partial_down, ks_d, m, norm_final, 0, st, pub_d ? &xd : nullptr))) return rc;
         for (int r = 0; r < R; ++r) {
             vlo_session *s = t->ss[r];
             vlo_engine *e = s->e;
-            GemvArgs a = gemv_args(e->lm_head, s->x + (size_t)r0 * H, H, nr);
+            GemvArgs a = gemv_args(e->lm_head, s->ws.x + (size_t)r0 * H, H, nr);
             a.out_bf16 = s->logits_local; a.ldo = e->V_l;
             TP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
         }
@@ -908,16 +910,16 @@ int vlo_tp_bench_exchange(vlo_tp_session *t, int m, int iters, double *avg_us, v
     hipStream_t st = (hipStream_t)stream;
     const size_t H = e0->cfg.hidden_size;
     for (vlo_session *s : t->ss) {            // finite inputs: partial sums of zeros, a residual stream of zeros
-        TP_TRY(hipMemsetAsync(s->partial, 0, (size_t)16 * H * 4, st));
-        TP_TRY(hipMemsetAsync(s->h, 0, (size_t)16 * H * 2, st));
+        TP_TRY(hipMemsetAsync(s->ws.partial, 0, (size_t)16 * H * 4, st));
+        TP_TRY(hipMemsetAsync(s->ws.h, 0, (size_t)16 * H * 2, st));
     }
     hipEvent_t e0v = nullptr, e1v = nullptr;
     TP_TRY(hipEventCreate(&e0v));
     if (hipEventCreate(&e1v) != hipSuccess) { hipEventDestroy(e0v); return vlo_fail(VLO_E_HIP, "hipEventCreate failed"); }
     int rc = VLO_OK;
-    for (int i = 0; i < 3 && !rc; ++i) rc = tp_reduce_norm(t, &vlo_session::partial, 1, m, norm_final, 0, st);   // warm-up
+    for (int i = 0; i < 3 && !rc; ++i) rc = tp_reduce_norm(t, partial_down, 1, m, norm_final, 0, st);   // warm-up
     hipError_t he = rc ? hipSuccess : hipEventRecord(e0v, st);
-    for (int i = 0; i < iters && !rc && he == hipSuccess; ++i) rc = tp_reduce_norm(t, &vlo_session::partial, 1, m, norm_final, 0, st);
+    for (int i = 0; i < iters && !rc && he == hipSuccess; ++i) rc = tp_reduce_norm(t, partial_down, 1, m, norm_final, 0, st);
     if (!rc && he == hipSuccess) he = hipEventRecord(e1v, st);
     if (!rc && he == hipSuccess) he = hipEventSynchronize(e1v);
     float ms = 0.f;
