@@ -13,7 +13,7 @@ Random weights make the speak/silent decision arbitrary, so the speech schedule 
 generated every 10th frame plus one for the t=0 user query; ``--mode silent`` and ``--mode free``
 are available.  N > 1 runs one independent stream per GPU (replicas, weak scaling: streams are
 independent, there is no exchange step) under torchrun, barrier + max-over-ranks timing — that is
-``value``.  The same invocation then measures ONE stream with the Llama tensor-parallel over the N
+``value``.  With ``--full`` the same invocation then measures ONE stream with the Llama tensor-parallel over the N
 GPUs (``--tp``) in child processes, once with RCCL all-reduces (``"tp"``) and once with the one-shot
 peer-to-peer all-reduce over xGMI (``"tp_p2p"``); a failure there is recorded, never fatal.
 
@@ -23,9 +23,13 @@ pre-roll), frames encoded ahead are dropped at the boundary, and the clock runs 
 the metric is defined on (K = 20: KV 15.5 k -> 15.8 k tokens).  ``full_stream`` reports all 1200 frames.
 ``--weight-dtype fp8`` streams the Llama projections as e4m3 + per-channel scales (BASELINE.json configs[4]'s LLM half).
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus ``roofline`` (dominant kernel =
-the gate/up weight-streaming GEMV, timed live with HIP events on its own stream) and
-``cpu_baseline`` (the CPU oracle on a bounded sample of the same workload, rank 0, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, warm-up, the pre-roll, the
+K timed steps, ``--dump-outputs`` when asked — the contract keys (``metric``, ``value``, ``unit``, ``higher_is_better``,
+``dtype``, ``ms_per_step``) and what those steps yield for free (latency percentiles, ``full_stream``, ``first_frame_ms``,
+``stream_hbm_roofline``).  ``--full`` adds every measurement that takes a run of its own, after the timed steps and the
+dump: ``roofline`` (dominant kernel = the gate/up weight-streaming GEMV, timed live with HIP events on its own stream, net
+of a calibrated empty bracket), ``encode_stage``, ``live_feed``, ``prefill``, ``cpu_baseline`` (the CPU oracle on a bounded
+sample of the same workload, rank 0, N=1 only) and, for N > 1, the tensor-parallel legs and their exchange latency.
 """
 import argparse
 import json
@@ -108,6 +112,42 @@ def stats_kernel_names(profiles_dir=None):
         return {r["kernel"] for r in csv.DictReader(open(path))}
     except Exception:
         return None
+
+
+def roofline(args, n_launch, prof_ms, bytes_per_launch, empty_us):
+    """--full: the `roofline` object — the dominant kernel (gate/up GEMV) from the HIP-event brackets the engine kept around its launches in the
+    timed region, net of ``empty_us`` (a calibrated empty bracket), beside the stored rocprofv3 / PMC figures under profiles/."""
+    avg_ms = prof_ms / max(n_launch, 1)
+    # a HIP-event bracket reads the kernel's duration plus the fixed cost of the bracket itself (what an EMPTY
+    # bracket reads on the same stream); net of that it agrees with rocprofv3's kernel-only average (profiles/)
+    net_ms = max(avg_ms - empty_us * 1e-3, 1e-6)
+    achieved = bytes_per_launch / (net_ms * 1e-3) / 1e9 if n_launch else None
+    # HBM traffic of the dominant kernel comes from PMC counters, which cannot be read from inside this process: it is the
+    # value of the builder's own `rocprofv3 --pmc` run of this command (stored under profiles/, see `traffic_source`)
+    traffic = traffic_source = None
+    pmc_path = os.path.join(ROOT, "profiles", "pmc_gemv_gate_up.json")
+    if os.path.exists(pmc_path):
+        try:
+            pmc = json.load(open(pmc_path))
+            # a stored counter figure is evidence for THIS code only if it names the kernel this code runs: the kernel of the newest committed
+            # rocprofv3 stats of the bench command (round 5's line quoted a round-3 file of a kernel with another template signature)
+            names = stats_kernel_names()
+            if names is not None and pmc.get("kernel") not in names:
+                traffic_source = (f"refused: profiles/pmc_gemv_gate_up.json is about `{pmc.get('kernel')}`, which is not a kernel of the newest "
+                                  "profiles/rN_kernel_stats_bench200*.csv — re-run the two PMC passes (tools/pmc_hbm_json.py)")
+            else:
+                traffic = pmc.get("hbm_bytes_per_launch")
+                traffic_source = (f"profiles/pmc_gemv_gate_up.json ({pmc.get('kernel')}, {pmc.get('launches')} launches, {pmc.get('round', 'round ?')}; stored result of a "
+                                  "rocprofv3 --pmc run, NOT measured in this run)")
+        except Exception:
+            traffic = None
+    rocprof = rocprof_cross_check(bytes_per_launch) if args.model == "llama-3-8b" and args.weight_dtype == "bf16" else {}
+    return {"bound": "hbm", "kernel": "gemv16_kernel<KF,EPI_SWIGLU> (gate/up projection + SwiGLU)" + (", fp8 weight image" if args.weight_dtype == "fp8" else ""),
+            "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
+            "traffic": traffic if args.weight_dtype == "bf16" else None, "traffic_source": traffic_source if args.weight_dtype == "bf16" else None,
+            "launches_timed": n_launch, "avg_launch_us": round(net_ms * 1e3, 2), "avg_bracket_us_raw": round(avg_ms * 1e3, 2),
+            "empty_bracket_us": round(empty_us, 2), "bytes_per_launch": bytes_per_launch, **rocprof}
 
 
 def aggregate_fps(frames_per_rank, world, elapsed_max):
@@ -285,7 +325,7 @@ def run_tp_leg(args, rank, world, local, allreduce="rccl", port_offset=17):
                MASTER_PORT=str(int(os.environ.get("MASTER_PORT", "29500")) + port_offset), VLO_BENCH_TP_LEG="0")
     steps = max(20, min(args.steps, args.tp_leg_steps))
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--steps", str(steps), "--warmup", "10", "--tp",
-           "--tp-allreduce", allreduce, "--no-cpu-baseline", "--model", args.model, "--mode", args.mode, "--fps", str(args.fps),
+           "--tp-allreduce", allreduce, "--full", "--no-cpu-baseline", "--model", args.model, "--mode", args.mode, "--fps", str(args.fps),
            "--prefetch-frames", str(args.prefetch_frames), "--tp-vit", getattr(args, "tp_vit", "frame-parallel"),
            "--vit", getattr(args, "vit", "siglip-l16-384"), "--weight-dtype", getattr(args, "weight_dtype", "bf16")]
     log(f"tp leg: {' '.join(cmd[1:])}")
@@ -379,6 +419,10 @@ def main():
     ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="storage of the streamed Llama projections; fp8 = e4m3 + per-channel scales (BASELINE.json configs[4]); the headline "
                          "metric is quoted on bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also run every secondary measurement: the dominant kernel's `roofline`, "
+                         "`encode_stage`, the `live_feed` re-runs, the `prefill` probe, the `cpu_baseline`, and for N > 1 the tensor-parallel legs "
+                         "and exchange latency.  Off by default: a plain run measures the headline figure only")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--prefetch-frames", type=int, default=56,
                     help="frames encoded ahead per batched ViT call while the Llama steps run (the reference batches pending frames the same way, "
@@ -554,12 +598,14 @@ def main():
     prof_eng = eng.engines[0] if tp else eng
     n_launch, prof_ms, bytes_per_launch = prof_eng.profile_read()
     eng.profile_enable(0)
-    empty_us = prof_eng.profile_calibrate()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, li, eng, cfg)
+    # From here to the result line: measurements with runs of their own, --full only.  (The HIP-event brackets around the dominant kernel stay on in the
+    # timed region of every run — they are part of the timed steps as the metric has always been taken; only reading them out as `roofline` is --full.)
+    empty_us = prof_eng.profile_calibrate() if args.full else None
     # encode stage in isolation (HIP events on its own stream): ms/frame and fraction of the dense fp16 MFMA peak
     vit_ms = vit1_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         B = max(1, batch_pf)
         enc = torch.cuda.Stream()
         with torch.cuda.stream(enc):
@@ -588,7 +634,7 @@ def main():
     # at all (frame t is encoded when it arrives, then its step runs: the encoder sits on the critical path of every frame).
     # Leg 2: one frame of look-ahead (frame t+1 encoded on the encode stream while the step of frame t runs).
     live_feed = None
-    if not tp and kv_start > 0 and not args.no_live_feed:
+    if args.full and not tp and kv_start > 0 and not args.no_live_feed:
         live_feed = {}
         saved = (li.prefetch, li.prefetch_frames)
         legs = (("no_lookahead", (False, 1, False)), ("recorded_file_lookahead", (True, batch_pf, False)), ("real_greedy_path", (True, 1, True)))
@@ -619,7 +665,7 @@ def main():
     # the long-input path (stream_evaluate's whole-dialogue forward, a long first prompt): ONE 4096-token teacher-forced block through
     # vlo_llm_step on a session of its own (prefill GEMMs + flash-style attention) — an extra key, outside the timed region
     prefill = None
-    if not tp and rank == 0 and not args.no_prefill_probe:
+    if args.full and not tp and rank == 0 and not args.no_prefill_probe:
         try:
             ps = eng.new_session()
             px = (torch.randn(PREFILL_PROBE_TOKENS, shape["hidden_size"], device="cuda") * 0.5).bfloat16()
@@ -641,7 +687,7 @@ def main():
     # tensor-parallel runs: latency of ONE exchange (all-reduce of [n, H] fp32 + residual add + RMSNorm) at the frame-step and the
     # decode-step size, every rank in lock-step — the number the xGMI all-reduce discussion of SURVEY.md §8e is about
     tp_exchange_us = None
-    if tp:
+    if args.full and tp:
         try:
             xs = eng.new_session()
             tp_exchange_us = {f"n{m}": round(eng.bench_exchange(xs, m, 200), 2) for m in (11, 1)}
@@ -664,31 +710,6 @@ def main():
 
     out = None
     if rank == 0:
-        avg_ms = prof_ms / max(n_launch, 1)
-        # a HIP-event bracket reads the kernel's duration plus the fixed cost of the bracket itself (what an EMPTY
-        # bracket reads on the same stream); net of that it agrees with rocprofv3's kernel-only average (profiles/)
-        net_ms = max(avg_ms - empty_us * 1e-3, 1e-6)
-        achieved = bytes_per_launch / (net_ms * 1e-3) / 1e9 if n_launch else None
-        # HBM traffic of the dominant kernel comes from PMC counters, which cannot be read from inside this process: it is the
-        # value of the builder's own `rocprofv3 --pmc` run of this command (stored under profiles/, see `traffic_source`)
-        traffic = traffic_source = None
-        pmc_path = os.path.join(ROOT, "profiles", "pmc_gemv_gate_up.json")
-        if os.path.exists(pmc_path):
-            try:
-                pmc = json.load(open(pmc_path))
-                # a stored counter figure is evidence for THIS code only if it names the kernel this code runs: the kernel of the newest committed
-                # rocprofv3 stats of the bench command (round 5's line quoted a round-3 file of a kernel with another template signature)
-                names = stats_kernel_names()
-                if names is not None and pmc.get("kernel") not in names:
-                    traffic_source = (f"refused: profiles/pmc_gemv_gate_up.json is about `{pmc.get('kernel')}`, which is not a kernel of the newest "
-                                      "profiles/rN_kernel_stats_bench200*.csv — re-run the two PMC passes (tools/pmc_hbm_json.py)")
-                else:
-                    traffic = pmc.get("hbm_bytes_per_launch")
-                    traffic_source = (f"profiles/pmc_gemv_gate_up.json ({pmc.get('kernel')}, {pmc.get('launches')} launches, {pmc.get('round', 'round ?')}; stored result of a "
-                                      "rocprofv3 --pmc run, NOT measured in this run)")
-            except Exception:
-                traffic = None
-        rocprof = rocprof_cross_check(bytes_per_launch) if args.model == "llama-3-8b" and args.weight_dtype == "bf16" else {}
         minutes = total / args.fps / 60.0
         out = {
             "metric": ("streaming FPS + p50 per-frame latency, Llama-3-8B+SigLIP-L, 10 min @ 2 FPS, 1/2/4/8 GPU"
@@ -726,12 +747,12 @@ def main():
                                                 message="fp32 [n, H] partial sums (180 KB at n = 11, 16 KB at n = 1): summed in fp32 as inside one GEMM, "
                                                         "the exchange is latency-bound at this size",
                                                 **(eng.p2p_status() if args.tp_allreduce == "p2p" else {}))} if tp else {})},
-            "encode_stage": {"batch": max(1, args.prefetch_frames), "ms_per_frame": round(vit_ms, 4),
+            **({"encode_stage": {"batch": max(1, args.prefetch_frames), "ms_per_frame": round(vit_ms, 4),
                              "tflops": round(vit_gflop / vit_ms, 1), "mfma_peak_tflops": MFMA_PEAK_TFLOPS,
                              "frac_of_mfma_peak": round(vit_gflop / vit_ms / MFMA_PEAK_TFLOPS, 4),
                              "one_frame_ms": round(vit1_ms, 4), "one_frame_frac_of_mfma_peak": round(vit_gflop / vit1_ms / MFMA_PEAK_TFLOPS, 4),
                              "note": ("SigLIP-L/16-384 + connector, 384.4 GFLOP/frame (SURVEY.md §8d), fp16 MFMA, measured alone" if args.vit == "siglip-l16-384"
-                                      else f"{args.vit} + connector, {vit_gflop:.1f} GFLOP/frame (encoder + patch embed + head K/V + connector), fp16 MFMA, measured alone")},
+                                      else f"{args.vit} + connector, {vit_gflop:.1f} GFLOP/frame (encoder + patch embed + head K/V + connector), fp16 MFMA, measured alone")}} if args.full else {}),
             **({"full_stream": full_stream} if full_stream else {}),
             **({"first_frame_ms": {"value": round(pre[1][0] * 1e3, 3),
                                    "note": "frame 0 of the stream, host wall time: its one-frame encode, the first Llama step (start prompt + 10 frame tokens "
@@ -739,18 +760,13 @@ def main():
             **({"live_feed": live_feed} if live_feed else {}),
             **({"prefill": prefill} if prefill else {}),
             "stream_hbm_roofline": {"algorithmic_llm_bytes": alg_bytes, "frac_of_hbm_peak": round(alg_bytes / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
-            "roofline": {"bound": "hbm", "kernel": "gemv16_kernel<KF,EPI_SWIGLU> (gate/up projection + SwiGLU)" + (", fp8 weight image" if args.weight_dtype == "fp8" else ""),
-                         "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
-                         "traffic": traffic if args.weight_dtype == "bf16" else None, "traffic_source": traffic_source if args.weight_dtype == "bf16" else None,
-                         "launches_timed": n_launch, "avg_launch_us": round(net_ms * 1e3, 2), "avg_bracket_us_raw": round(avg_ms * 1e3, 2),
-                         "empty_bracket_us": round(empty_us, 2), "bytes_per_launch": bytes_per_launch, **rocprof},
+            **({"roofline": roofline(args, n_launch, prof_ms, bytes_per_launch, empty_us)} if args.full else {}),
         }
     # N > 1, replica mode: also measure ONE stream tensor-parallel over the same N GPUs (BASELINE.json north_star).  It
     # runs in child processes (one per rank, own rendezvous port) so that a failure or hang of the RCCL leg — which no
     # single-GPU box can exercise beforehand — can never cost the replica line above.
     tp_leg = tp_p2p_leg = None
-    if world > 1 and not tp and not args.no_tp_leg and os.environ.get("VLO_BENCH_TP_LEG", "1") != "0":
+    if args.full and world > 1 and not tp and not args.no_tp_leg and os.environ.get("VLO_BENCH_TP_LEG", "1") != "0":
         tp_leg = run_tp_leg(args, rank, world, local, "rccl", 17)
         if dist is not None:
             dist.barrier()                     # every rank's first child is gone before the second leg claims the GPUs
@@ -780,9 +796,9 @@ def main():
             effs = {name: leg.get("scaling_efficiency") for name, leg in (("tp", tp_leg), ("tp_p2p", tp_p2p_leg)) if leg and leg.get("scaling_efficiency")}
             out["tp_scaling_efficiency"] = max(effs.values()) if effs else None
             out["tp_scaling_efficiency_by_leg"] = effs or None
-        if world == 1 and not args.no_cpu_baseline and args.vit != "siglip-l16-384":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.vit != "siglip-l16-384":
             out["cpu_baseline"] = {"value": None, "note": "the CPU baseline is the reference's own path, which only accepts SigLIP-L (models/vision_live.py:56-60)"}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu_baseline: building CPU oracle")
             try:
                 out["cpu_baseline"] = cpu_baseline(args.model, frames[:max(args.cpu_sample_frames, 10)].cpu(), toks, args.mode,

@@ -6,21 +6,22 @@
 # Every STEP is one quoted string, first word = verb:
 #   gate                         the driver's gate, literally: `python -m pytest tests -m gpu -x -q`, then __graft_entry__.smoke()
 #   pytest NAME ARGS...          python -m pytest ARGS (log: pytest_NAME.log); env assignments may precede via `env`
-#   bench NAME ARGS...           python bench.py ARGS > bench_NAME.json (+ a one-line digest on stdout)
+#   bench NAME ARGS...           python bench.py ARGS > bench_NAME.json (+ a one-line digest on stdout; its roofline / encode / live_feed / cpu
+#                                fields are measured only when ARGS has --full)
 #   run NAME CMD...              any command, stdout+stderr -> NAME.txt (probes, sweeps)
 #   prof NAME CMD...             rocprofv3 --kernel-trace --stats -- CMD  -> kernel_stats_NAME.csv (tools/rocpd_stats.py)
 #   pmc NAME CTR [CTR...] -- CMD one rocprofv3 --kernel-trace --pmc pass (never combined with other trace domains) -> pmc_NAME.csv
 #   long [PYTEST ARGS]           the long parity file alone (default-on since round 6; with VLO_FOLLOWER_DEVICE=cpu ~23 GPU-minutes)
 # A step's own time limit: prefix the string with `T=<seconds>` (default 600).  Steps never abort the script; each prints its exit code.
 #
-# Example (one gpurun call):
-#   gpurun --timeout 1500 -- "tools/gpu_evidence.sh r4a 'gate' 'bench k20 --gpus 1 --steps 20 --warmup 5' \
+# Example (one call):
+#   tools/gpu_evidence.sh r4a 'gate' 'bench k20 --gpus 1 --steps 20 --warmup 5 --full' \
 #       'prof bench200 python bench.py --gpus 1 --steps 200 --warmup 5 --no-cpu-baseline' \
-#       'pmc fetch_llm FETCH_SIZE -- python tools/probe_llm.py --frames 24'"
+#       'pmc fetch_llm FETCH_SIZE -- python tools/probe_llm.py --frames 24'
 set -u
 cd "$(dirname "$0")/.."
 ROOT=$PWD
-[ $# -ge 2 ] || { sed -n 2,22p "$0"; exit 2; }
+[ $# -ge 2 ] || { sed -n 2,20p "$0"; exit 2; }
 OUT=$ROOT/gpurun_out/$1; shift
 mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0 TMPDIR=/tmp
