@@ -1,23 +1,36 @@
-// attn_body.inc — the body of the chunk attention (see llm_ops.hip), included TEXTUALLY by
-// attn_chunk_kernel (llm_ops.hip) with VLO_ATTN_BX / BY / BZ / GX = blockIdx.x / .y / .z / gridDim.x, VLO_ATTN_EXIT = return
-// (the kernel bodies live in .inc files so that variants walking the same virtual grid can share them).
-// Expects in scope: template parameters HD, HPW; the kernel's parameters by name; `float4 *lds_o`.
-// VLO_ATTN_F8 = 1 (attn_chunk_f8_kernel): the pool holds e4m3 bytes (8-byte K / V^T pieces expanded to the bf16 fragments in registers),
-// `scale` already carries the layer's k_scale and `vscale` multiplies the partial output.
+// attn_body.inc — the ONE definition of the chunk attention (algorithm: see llm_ops.hip above attn_chunk_kernel), included textually by its four
+// kernels: attn_chunk_kernel, attn_chunk_f8_kernel, attn_chunk_seg_kernel, attn_chunk_seg_f8_kernel.  (A __device__ function would be the
+// natural form, but no form tried keeps the kernels' machine code: profiles/attn_family_refactor.md.)
+// The including kernel sets, and this file consumes (#undef at the end):
+//   VLO_ATTN_F8        1: the pool holds e4m3 bytes (8-byte K / V^T pieces expanded to the bf16 fragments in registers), 0: bf16
+//   VLO_ATTN_SUBCHUNK  which 16-query sub-chunk of a longer block of new tokens this workgroup serves: blockIdx.z in a solo launch (block
+//                      path: queries z*16 .. z*16+n-1), 0 in a segmented launch (a segment IS one sub-chunk)
+// Every name read from the including kernel is listed and type-checked here, so a kernel that does not provide one fails to compile:
+    static_assert(HD % 32 == 0 && (HPW == 1 || HPW == 2), "template parameters HD, HPW");
+    VLO_ATTN_NAME(q, const bf16_t *);            // the sub-chunk-0 query rows [n][nh * HD]
+    VLO_ATTN_NAME(kv, KvGeom);                   // the pool; kv.page_table = the session's
+    VLO_ATTN_NAME(layer, int);  VLO_ATTN_NAME(nh, int);  VLO_ATTN_NAME(G, int);  VLO_ATTN_NAME(KS, int);
+    VLO_ATTN_NAME(pos0, int64_t);  VLO_ATTN_NAME(n, int);  VLO_ATTN_NAME(chunk, int);
+    VLO_ATTN_NAME(scale, float);
+    VLO_ATTN_NAME(part_o, float *);  VLO_ATTN_NAME(part_ml, float *);   // the launch's first partial state
+#if VLO_ATTN_F8
+    VLO_ATTN_NAME(kv_scale, const float *);
+    const float vscale = attn_f8_scales(kv_scale, layer, scale);   // `scale` now carries k_scale; vscale multiplies the partial output
+#endif
+    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];        // [(KS-1)*NHG][HPW][NDT][64] float4, then m/l
     constexpr int NKK = HD / 32, NDT = HD / 16;
     const int NHG = G / HPW;
     float *lds_ml = reinterpret_cast<float *>(lds_o + (size_t)(KS - 1) * NHG * HPW * NDT * 64);   // [(KS-1)*NHG][HPW][16][2]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int hg = w % NHG, ks = w / NHG;
-    const int split = VLO_ATTN_BX, kvh = VLO_ATTN_BY;
-    // VLO_ATTN_BZ = 16-query sub-chunk of a longer block of new tokens (block path): queries z*16 .. z*16+n-1
+    const int split = blockIdx.x, kvh = blockIdx.y;
     {
-        const int z = VLO_ATTN_BZ;
+        const int z = VLO_ATTN_SUBCHUNK;
         q += (size_t)z * 16 * nh * HD;
         pos0 += 16 * z;
         n = min(16, n - 16 * z);
-        part_o += (size_t)z * VLO_ATTN_GX * nh * 16 * HD;
-        part_ml += (size_t)z * VLO_ATTN_GX * nh * 16 * 2;
+        part_o += (size_t)z * gridDim.x * nh * 16 * HD;
+        part_ml += (size_t)z * gridDim.x * nh * 16 * 2;
     }
     const int L = (int)(pos0 + n);
     const int c0 = split * chunk, c1 = min(L, c0 + chunk);
@@ -176,7 +189,7 @@
             }
         }
         __syncthreads();
-        if (ks > 0) VLO_ATTN_EXIT;
+        if (ks > 0) return;
 #pragma unroll
         for (int h = 0; h < HPW; ++h) {
             float M = mrun[h];
@@ -218,3 +231,5 @@
             *reinterpret_cast<float4 *>(part_o + row * HD + dt * 16 + qd * 4) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
+#undef VLO_ATTN_F8
+#undef VLO_ATTN_SUBCHUNK

@@ -1,7 +1,20 @@
-// attn_cols_body.inc — the body of the column-packed chunk attention (see llm_ops.hip), included TEXTUALLY by attn_cols_kernel (bf16 pool,
-// VLO_ATTN_F8 = 0) and attn_cols_f8_kernel (e4m3 pool, VLO_ATTN_F8 = 1: 8-byte K / V^T pieces expanded to the bf16 fragments in registers;
-// `scale` already carries the layer's k_scale, `vscale` multiplies the partial output).
-// Expects in scope: template parameters HD, NCT; the kernel's parameters by name.
+// attn_cols_body.inc — the ONE definition of the column-packed chunk attention (algorithm: see llm_ops.hip above attn_cols_kernel), included
+// textually by its four kernels: attn_cols_kernel, attn_cols_f8_kernel, attn_cols_seg_kernel, attn_cols_seg_f8_kernel.  (Why not a __device__
+// function: profiles/attn_family_refactor.md.)
+// The including kernel sets, and this file consumes (#undef at the end):
+//   VLO_ATTN_F8        1: the pool holds e4m3 bytes (8-byte K / V^T pieces expanded to the bf16 fragments in registers), 0: bf16
+// Every name read from the including kernel is listed and type-checked here, so a kernel that does not provide one fails to compile:
+    static_assert(HD % 32 == 0 && NCT >= 1 && NCT <= 3, "template parameters HD, NCT");
+    VLO_ATTN_NAME(q, const bf16_t *);            // the query rows [n][nh * HD]
+    VLO_ATTN_NAME(kv, KvGeom);                   // the pool; kv.page_table = the session's
+    VLO_ATTN_NAME(layer, int);  VLO_ATTN_NAME(nh, int);  VLO_ATTN_NAME(G, int);
+    VLO_ATTN_NAME(pos0, int64_t);  VLO_ATTN_NAME(n, int);  VLO_ATTN_NAME(chunk, int);
+    VLO_ATTN_NAME(scale, float);
+    VLO_ATTN_NAME(part_o, float *);  VLO_ATTN_NAME(part_ml, float *);   // the launch's (segment's) first partial state
+#if VLO_ATTN_F8
+    VLO_ATTN_NAME(kv_scale, const float *);
+    const float vscale = attn_f8_scales(kv_scale, layer, scale);   // `scale` now carries k_scale; vscale multiplies the partial output
+#endif
     constexpr int NKK = HD / 32, NDT = HD / 16, KS = 8;
     extern __shared__ __attribute__((aligned(16))) float4 lds_o[];         // the block's one dynamic LDS array (shared name with attn_chunk_kernel)
     uint4 *qs = reinterpret_cast<uint4 *>(lds_o);                          // [NCT][NKK][64]   Q fragments (MFMA B operand)
@@ -199,3 +212,4 @@
             *reinterpret_cast<float4 *>(part_o + row * HD + dt * 16 + qd * 4) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
+#undef VLO_ATTN_F8

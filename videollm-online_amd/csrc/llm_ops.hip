@@ -38,6 +38,21 @@ hipError_t add_rmsnorm_launch(unsigned short *h, const float *partial, int kspli
 }
 
 // ------------------------------------------------------------------------------------
+// What the live-step attention kernels share.  Two bodies (attn_body.inc, attn_cols_body.inc), each stamped into four kernels: solo / segmented
+// launch x bf16 / fp8 pool.  The bodies check the names they read from their kernel with these:
+// ------------------------------------------------------------------------------------
+template <class T> struct attn_plain { typedef T type; };                        // the type without __restrict__ (kernel parameters carry it)
+template <class T> struct attn_plain<T *__restrict__> { typedef T *type; };
+#define VLO_ATTN_NAME(x, ...) static_assert(std::is_same<typename attn_plain<std::remove_cv_t<decltype(x)>>::type, __VA_ARGS__>::value, \
+                                            "attention body: `" #x "` must be a " #__VA_ARGS__ " of the including kernel")
+// fp8 pool (kv_scale = the pool's [layer][2] {k_scale, v_scale}): folds k_scale into the score scale — (q . k_code) k_scale / sqrt(d) — and
+// returns v_scale, which multiplies the partial output
+VLO_DEV float attn_f8_scales(const float *__restrict__ kv_scale, int layer, float &scale) {
+    scale *= kv_scale[2 * layer];
+    return kv_scale[2 * layer + 1];
+}
+
+// ------------------------------------------------------------------------------------
 // chunk attention.  grid = (nsplit, nkv); block = NHG x KS waves:
 //   NHG = G / HPW head groups (wave hg owns q heads kvh*G + hg*HPW .. +HPW),
 //   KS  = in-block key sub-splits (wave ks walks every KS-th 32-key block of the block's chunk),
@@ -53,42 +68,18 @@ template <int HD, int HPW>
 __global__ __launch_bounds__(512) void attn_chunk_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int KS,
                                                          int64_t pos0, int n, int chunk, float scale,
                                                          float *__restrict__ part_o, float *__restrict__ part_ml) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];        // [(KS-1)*NHG][HPW][NDT][64] float4, then m/l
-#define VLO_ATTN_BX blockIdx.x
-#define VLO_ATTN_BY blockIdx.y
-#define VLO_ATTN_BZ blockIdx.z
-#define VLO_ATTN_GX gridDim.x
-#define VLO_ATTN_EXIT return
 #define VLO_ATTN_F8 0
+#define VLO_ATTN_SUBCHUNK blockIdx.z
 #include "attn_body.inc"
-#undef VLO_ATTN_F8
-#undef VLO_ATTN_BX
-#undef VLO_ATTN_BY
-#undef VLO_ATTN_BZ
-#undef VLO_ATTN_GX
-#undef VLO_ATTN_EXIT
 }
 // the same over an fp8 e4m3 pool (vlo_config.kv_dtype = 1): kv_scale = the pool's [layer][2] {k_scale, v_scale}
 template <int HD, int HPW>
 __global__ __launch_bounds__(512) void attn_chunk_f8_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int KS,
                                                             int64_t pos0, int n, int chunk, float scale,
                                                             float *__restrict__ part_o, float *__restrict__ part_ml, const float *__restrict__ kv_scale) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
-    scale *= kv_scale[2 * layer];                                          // (q . k_code) k_scale / sqrt(d)
-    const float vscale = kv_scale[2 * layer + 1];
-#define VLO_ATTN_BX blockIdx.x
-#define VLO_ATTN_BY blockIdx.y
-#define VLO_ATTN_BZ blockIdx.z
-#define VLO_ATTN_GX gridDim.x
-#define VLO_ATTN_EXIT return
 #define VLO_ATTN_F8 1
+#define VLO_ATTN_SUBCHUNK blockIdx.z
 #include "attn_body.inc"
-#undef VLO_ATTN_F8
-#undef VLO_ATTN_BX
-#undef VLO_ATTN_BY
-#undef VLO_ATTN_BZ
-#undef VLO_ATTN_GX
-#undef VLO_ATTN_EXIT
 }
 
 // ------------------------------------------------------------------------------------
@@ -106,18 +97,14 @@ __global__ __launch_bounds__(512) void attn_cols_kernel(const bf16_t *__restrict
                                                         int chunk, float scale, float *__restrict__ part_o, float *__restrict__ part_ml) {
 #define VLO_ATTN_F8 0
 #include "attn_cols_body.inc"
-#undef VLO_ATTN_F8
 }
 // the same over an fp8 e4m3 pool (vlo_config.kv_dtype = 1): kv_scale = the pool's [layer][2] {k_scale, v_scale}
 template <int HD, int NCT>
 __global__ __launch_bounds__(512) void attn_cols_f8_kernel(const bf16_t *__restrict__ q, KvGeom kv, int layer, int nh, int G, int64_t pos0, int n,
                                                            int chunk, float scale, float *__restrict__ part_o, float *__restrict__ part_ml,
                                                            const float *__restrict__ kv_scale) {
-    scale *= kv_scale[2 * layer];                                          // (q . k_code) k_scale / sqrt(d)
-    const float vscale = kv_scale[2 * layer + 1];
 #define VLO_ATTN_F8 1
 #include "attn_cols_body.inc"
-#undef VLO_ATTN_F8
 }
 
 // Merge of the split-KV partials.  grid = (nh, n); block = 256 threads = SL split-lanes x CL column-lanes of 4 columns (HD = 128:
@@ -144,14 +131,6 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float *__restri
     }
 #include "attn_combine_body.inc"
 }
-static hipError_t attn_combine_launch(const float *part_o, const float *part_ml, int nsplit, int nh, int hd, int n, unsigned short *out,
-                                      int pack_row0, hipStream_t st) {
-    if (hd == 128) hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(nh, n), dim3(256), 0, st, part_o, part_ml, nsplit, nh, out, pack_row0);
-    else if (hd == 64) hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(nh, n), dim3(256), 0, st, part_o, part_ml, nsplit, nh, out, pack_row0);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
 // max over lanes l, l ^ 16, l ^ 32, l ^ 48 (the four lanes that hold one score column of a 16 x 16 MFMA tile) by two row swaps
 VLO_DEV float quad_lanes_maxf(float x) {
     const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -278,162 +257,68 @@ hipError_t attention_geometry(const KvGeom &kv, int num_heads, int64_t pos0, int
     return hipSuccess;
 }
 
-hipError_t attention_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n,
-                            float *part_o, float *part_ml, unsigned short *out, hipStream_t st, int pack_row0, int part_cap) {
-    AttnGeom ag;
-    const hipError_t ge = attention_geometry(kv, num_heads, pos0, n, &ag, part_cap);
-    if (ge != hipSuccess) return ge;
-    const int nkv = kv.num_kv_heads, hd = kv.head_dim, G = ag.G, hpw = ag.hpw, nhg = ag.nhg, KS = ag.KS, nz = ag.nz, chunk = ag.chunk,
-              nsplit = ag.nsplit;
-    const float scale = ag.scale;
-    dim3 grid(nsplit, nkv, nz), block(nhg * KS * 64);
-    const size_t lds = ag.lds_bytes;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void *)attn_chunk_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_kernel<64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_chunk_f8_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<128, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)attn_cols_f8_kernel<64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-        attr_done = true;
-    }
-    const KvGeom &kg = kv;
-    const bool f8 = kv.dtype == VLO_KV_FP8;
-    if (f8 && !kv.scale) return hipErrorInvalidValue;
-#define VLO_ATTN_COLS(HD_, NCT_)                                                                                                                 \
-    do {                                                                                                                                         \
-        if (f8) hipLaunchKernelGGL((attn_cols_f8_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale, \
-                                   part_o, part_ml, kv.scale);                                                                                   \
-        else hipLaunchKernelGGL((attn_cols_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale,      \
-                                part_o, part_ml);                                                                                                \
-    } while (0)
-    if (ag.nct) {
-        if (hd == 128 && ag.nct == 1) VLO_ATTN_COLS(128, 1);
-        else if (hd == 128 && ag.nct == 2) VLO_ATTN_COLS(128, 2);
-        else if (hd == 128) VLO_ATTN_COLS(128, 3);
-        else if (ag.nct == 1) VLO_ATTN_COLS(64, 1);
-        else if (ag.nct == 2) VLO_ATTN_COLS(64, 2);
-        else VLO_ATTN_COLS(64, 3);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        return attn_combine_launch(part_o, part_ml, nsplit, num_heads, hd, n, out, pack_row0, st);
-    }
-#undef VLO_ATTN_COLS
-#define VLO_ATTN(HD_, HPW_)                                                                                                                      \
-    do {                                                                                                                                         \
-        if (f8) hipLaunchKernelGGL((attn_chunk_f8_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk,      \
-                                   scale, part_o, part_ml, kv.scale);                                                                            \
-        else hipLaunchKernelGGL((attn_chunk_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk, scale,     \
-                                part_o, part_ml);                                                                                                \
-    } while (0)
-    if (hd == 128 && hpw == 2) VLO_ATTN(128, 2);
-    else if (hd == 128 && hpw == 1) VLO_ATTN(128, 1);
-    else if (hd == 64 && hpw == 2) VLO_ATTN(64, 2);
-    else if (hd == 64 && hpw == 1) VLO_ATTN(64, 1);
-    else return hipErrorInvalidValue;
-#undef VLO_ATTN
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return attn_combine_launch(part_o, part_ml, nsplit, num_heads, hd, n, out, pack_row0, st);
-}
-
 // ------------------------------------------------------------------------------------
 // Segmented attention (batched steps, engine.hip vlo_batch_step): blockIdx.z = one segment of the device table (llm_ops.h AttnSeg), i.e.
 // one 16-query sub-chunk of one session with its own page table, position, query count, first row and split geometry — the geometry the
 // session's solo launch would use, so each segment walks exactly the keys, splits and merges of that launch.  grid.x = the widest segment's
 // split count; the blocks past a segment's last split leave at once (a uniform exit: no barrier has been reached).  The bodies are the solo
-// kernels' .inc files; only the kernel parameters they read are re-pointed at the segment.
+// kernels' .inc files; the names they read as kernel parameters of a solo launch come from the segment (attn_seg_args).
 // ------------------------------------------------------------------------------------
-#define VLO_SEG_PROLOGUE                                                                                  \
-    const AttnSeg sg = segs[blockIdx.z];                                                                  \
-    if ((int)blockIdx.x >= sg.nsplit) return;                                                             \
-    kv.page_table = sg.page_table;                                                                        \
-    const bf16_t *__restrict__ q = q_rows + (size_t)sg.row0 * nh * HD;                                    \
-    int64_t pos0 = sg.pos0;                                                                               \
-    int n = sg.n;                                                                                         \
-    const int chunk = sg.chunk;                                                                           \
-    float *__restrict__ part_o = part_o_all + (size_t)sg.part0 * nh * 16 * HD;                            \
-    float *__restrict__ part_ml = part_ml_all + (size_t)sg.part0 * nh * 16 * 2;
+// what a solo kernel gets as parameters, for one segment.  A kernel reads its segment and leaves first — `if (blockIdx.x >= sg.nsplit) return` —
+// and takes this view afterwards (computed ahead of the exit it changes the kernels' scalar code: profiles/attn_family_refactor.md)
+struct AttnSegArgs { const bf16_t *q; int64_t pos0; int n, chunk; float *part_o, *part_ml; };
+template <int HD>
+VLO_DEV AttnSegArgs attn_seg_args(const AttnSeg &sg, const bf16_t *q_rows, int nh, float *part_o_all, float *part_ml_all) {
+    return {q_rows + (size_t)sg.row0 * nh * HD, sg.pos0, sg.n, sg.chunk, part_o_all + (size_t)sg.part0 * nh * 16 * HD,
+            part_ml_all + (size_t)sg.part0 * nh * 16 * 2};
+}
 
 template <int HD, int HPW>
 __global__ __launch_bounds__(512) void attn_chunk_seg_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G, int KS,
                                                              const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
                                                              float *__restrict__ part_ml_all) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
-    VLO_SEG_PROLOGUE
-#define VLO_ATTN_BX blockIdx.x
-#define VLO_ATTN_BY blockIdx.y
-#define VLO_ATTN_BZ 0
-#define VLO_ATTN_GX gridDim.x
-#define VLO_ATTN_EXIT return
+    const AttnSeg sg = segs[blockIdx.z];
+    if ((int)blockIdx.x >= sg.nsplit) return;
+    kv.page_table = sg.page_table;
+    auto [q, pos0, n, chunk, part_o, part_ml] = attn_seg_args<HD>(sg, q_rows, nh, part_o_all, part_ml_all);
 #define VLO_ATTN_F8 0
+#define VLO_ATTN_SUBCHUNK 0
 #include "attn_body.inc"
-#undef VLO_ATTN_F8
-#undef VLO_ATTN_BX
-#undef VLO_ATTN_BY
-#undef VLO_ATTN_BZ
-#undef VLO_ATTN_GX
-#undef VLO_ATTN_EXIT
 }
 template <int HD, int HPW>
 __global__ __launch_bounds__(512) void attn_chunk_seg_f8_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G, int KS,
                                                                 const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
                                                                 float *__restrict__ part_ml_all, const float *__restrict__ kv_scale) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds_o[];
-    VLO_SEG_PROLOGUE
-    scale *= kv_scale[2 * layer];
-    const float vscale = kv_scale[2 * layer + 1];
-#define VLO_ATTN_BX blockIdx.x
-#define VLO_ATTN_BY blockIdx.y
-#define VLO_ATTN_BZ 0
-#define VLO_ATTN_GX gridDim.x
-#define VLO_ATTN_EXIT return
+    const AttnSeg sg = segs[blockIdx.z];
+    if ((int)blockIdx.x >= sg.nsplit) return;
+    kv.page_table = sg.page_table;
+    auto [q, pos0, n, chunk, part_o, part_ml] = attn_seg_args<HD>(sg, q_rows, nh, part_o_all, part_ml_all);
 #define VLO_ATTN_F8 1
+#define VLO_ATTN_SUBCHUNK 0
 #include "attn_body.inc"
-#undef VLO_ATTN_F8
-#undef VLO_ATTN_BX
-#undef VLO_ATTN_BY
-#undef VLO_ATTN_BZ
-#undef VLO_ATTN_GX
-#undef VLO_ATTN_EXIT
 }
 template <int HD, int NCT>
 __global__ __launch_bounds__(512) void attn_cols_seg_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G,
                                                             const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
                                                             float *__restrict__ part_ml_all) {
-    VLO_SEG_PROLOGUE
+    const AttnSeg sg = segs[blockIdx.z];
+    if ((int)blockIdx.x >= sg.nsplit) return;
+    kv.page_table = sg.page_table;
+    auto [q, pos0, n, chunk, part_o, part_ml] = attn_seg_args<HD>(sg, q_rows, nh, part_o_all, part_ml_all);
 #define VLO_ATTN_F8 0
 #include "attn_cols_body.inc"
-#undef VLO_ATTN_F8
 }
 template <int HD, int NCT>
 __global__ __launch_bounds__(512) void attn_cols_seg_f8_kernel(const bf16_t *__restrict__ q_rows, KvGeom kv, int layer, int nh, int G,
                                                                const AttnSeg *__restrict__ segs, float scale, float *__restrict__ part_o_all,
                                                                float *__restrict__ part_ml_all, const float *__restrict__ kv_scale) {
-    VLO_SEG_PROLOGUE
-    scale *= kv_scale[2 * layer];
-    const float vscale = kv_scale[2 * layer + 1];
+    const AttnSeg sg = segs[blockIdx.z];
+    if ((int)blockIdx.x >= sg.nsplit) return;
+    kv.page_table = sg.page_table;
+    auto [q, pos0, n, chunk, part_o, part_ml] = attn_seg_args<HD>(sg, q_rows, nh, part_o_all, part_ml_all);
 #define VLO_ATTN_F8 1
 #include "attn_cols_body.inc"
-#undef VLO_ATTN_F8
 }
-#undef VLO_SEG_PROLOGUE
 
 // merge of the split partials of every segment: grid = (nh, 16, segments); query row r of segment s goes to row s.row0 + r
 template <int HD>
@@ -445,7 +330,7 @@ __global__ __launch_bounds__(256) void attn_combine_seg_kernel(const float *__re
     const AttnSeg sg = segs[blockIdx.z];
     const int qrow = blockIdx.y, nsplit = sg.nsplit;
     if (qrow >= sg.n) return;
-    part_o += (size_t)sg.part0 * nh * 16 * HD;
+    part_o += (size_t)sg.part0 * nh * 16 * HD;          // (not through attn_seg_args: the compiler orders this kernel's scalar code differently then)
     part_ml += (size_t)sg.part0 * nh * 16 * 2;
     const int pack_row0 = packed ? sg.row0 : -1;
     if (!packed) out += (size_t)sg.row0 * nh * HD;
@@ -510,70 +395,117 @@ hipError_t attention_seg_plan(const KvGeom &kv, int num_heads, int B, const int 
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------------------------
+// The live-step attention kernels, every instantiation ONCE: a row = one (head dim, HPW) shape of the chunk family or one (head dim, NCT) shape
+// of the column-packed family, with its solo / segmented x bf16 / fp8 kernels.  Both launchers pick their kernel here, and the dynamic-LDS
+// limit is raised by walking the same rows.  A new shape is one more row; a new variant of a family is one more column.
+// ------------------------------------------------------------------------------------
+struct AttnKernels {
+    int hd, p;                                           // p = HPW (chunk rows) or NCT (column-packed rows)
+    decltype(&attn_chunk_kernel<128, 1>) chunk;          // chunk rows fill these four, column-packed rows the other four
+    decltype(&attn_chunk_f8_kernel<128, 1>) chunk_f8;
+    decltype(&attn_chunk_seg_kernel<128, 1>) chunk_seg;
+    decltype(&attn_chunk_seg_f8_kernel<128, 1>) chunk_seg_f8;
+    decltype(&attn_cols_kernel<128, 1>) cols;
+    decltype(&attn_cols_f8_kernel<128, 1>) cols_f8;
+    decltype(&attn_cols_seg_kernel<128, 1>) cols_seg;
+    decltype(&attn_cols_seg_f8_kernel<128, 1>) cols_seg_f8;
+};
+template <int HD, int HPW>
+constexpr AttnKernels attn_chunk_row() {
+    return {HD, HPW, attn_chunk_kernel<HD, HPW>, attn_chunk_f8_kernel<HD, HPW>, attn_chunk_seg_kernel<HD, HPW>, attn_chunk_seg_f8_kernel<HD, HPW>,
+            nullptr, nullptr, nullptr, nullptr};
+}
+template <int HD, int NCT>
+constexpr AttnKernels attn_cols_row() {
+    return {HD, NCT, nullptr, nullptr, nullptr, nullptr,
+            attn_cols_kernel<HD, NCT>, attn_cols_f8_kernel<HD, NCT>, attn_cols_seg_kernel<HD, NCT>, attn_cols_seg_f8_kernel<HD, NCT>};
+}
+static constexpr AttnKernels kAttnKernels[] = {
+    attn_chunk_row<128, 2>(), attn_chunk_row<128, 1>(), attn_chunk_row<64, 2>(), attn_chunk_row<64, 1>(),
+    attn_cols_row<128, 1>(), attn_cols_row<128, 2>(), attn_cols_row<128, 3>(), attn_cols_row<64, 1>(), attn_cols_row<64, 2>(), attn_cols_row<64, 3>()};
+struct AttnCombine { int hd; decltype(&attn_combine_kernel<128>) solo; decltype(&attn_combine_seg_kernel<128>) seg; };
+static constexpr AttnCombine kAttnCombine[] = {{128, attn_combine_kernel<128>, attn_combine_seg_kernel<128>},
+                                               {64, attn_combine_kernel<64>, attn_combine_seg_kernel<64>}};
+
+// the row of this shape — nct != 0: column-packed (hd, nct), else chunk (hd, hpw) — or nullptr: not instantiated.  The first lookup of the
+// process raises every kernel's dynamic-LDS limit to the CU's 160 KiB (function-local static: safe from sessions stepping on threads of their own).
+static const AttnKernels *attn_kernels(int hd, int hpw, int nct) {
+    static const bool lds_raised = [] {
+        for (const AttnKernels &r : kAttnKernels)
+            for (const void *k : {(const void *)r.chunk, (const void *)r.chunk_f8, (const void *)r.chunk_seg, (const void *)r.chunk_seg_f8,
+                                  (const void *)r.cols, (const void *)r.cols_f8, (const void *)r.cols_seg, (const void *)r.cols_seg_f8})
+                if (k) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)lds_raised;
+    for (const AttnKernels &r : kAttnKernels)
+        if (r.hd == hd && (nct ? r.cols && r.p == nct : r.chunk && r.p == hpw)) return &r;
+    return nullptr;
+}
+static const AttnCombine *attn_combine(int hd) {
+    for (const AttnCombine &c : kAttnCombine)
+        if (c.hd == hd) return &c;
+    return nullptr;
+}
+
+hipError_t attention_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, int64_t pos0, int n,
+                            float *part_o, float *part_ml, unsigned short *out, hipStream_t st, int pack_row0, int part_cap) {
+    AttnGeom ag;
+    const hipError_t ge = attention_geometry(kv, num_heads, pos0, n, &ag, part_cap);
+    if (ge != hipSuccess) return ge;
+    const int nkv = kv.num_kv_heads, hd = kv.head_dim, G = ag.G, hpw = ag.hpw, nhg = ag.nhg, KS = ag.KS, nz = ag.nz, chunk = ag.chunk,
+              nsplit = ag.nsplit;
+    const float scale = ag.scale;
+    dim3 grid(nsplit, nkv, nz), block(nhg * KS * 64);
+    const size_t lds = ag.lds_bytes;
+    const AttnKernels *k = attn_kernels(hd, hpw, ag.nct);
+    const KvGeom &kg = kv;
+    const bool f8 = kv.dtype == VLO_KV_FP8;
+    if (!k || (f8 && !kv.scale)) return hipErrorInvalidValue;
+    if (ag.nct) {
+        if (f8) hipLaunchKernelGGL(k->cols_f8, grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale, part_o, part_ml, kv.scale);
+        else hipLaunchKernelGGL(k->cols, grid, dim3(512), lds, st, q, kg, layer, num_heads, G, pos0, n, chunk, scale, part_o, part_ml);
+    } else {
+        if (f8) hipLaunchKernelGGL(k->chunk_f8, grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk, scale, part_o, part_ml, kv.scale);
+        else hipLaunchKernelGGL(k->chunk, grid, block, lds, st, q, kg, layer, num_heads, G, KS, pos0, n, chunk, scale, part_o, part_ml);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const AttnCombine *c = attn_combine(hd);
+    if (!c) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(c->solo, dim3(num_heads, n), dim3(256), 0, st, part_o, part_ml, nsplit, num_heads, out, pack_row0);
+    return hipGetLastError();
+}
+
 hipError_t attention_seg_launch(const unsigned short *q, const KvPool &kv, int layer, int num_heads, const AttnSeg *segs_dev, int nseg,
                                 const AttnSegRun *runs, int nrun, float *part_o, float *part_ml, unsigned short *out, bool packed, hipStream_t st) {
     const int nkv = kv.num_kv_heads, hd = kv.head_dim;
     const bool f8 = kv.dtype == VLO_KV_FP8;
     if (f8 && !kv.scale) return hipErrorInvalidValue;
     if (nseg < 1 || nseg > VLO_ATTN_SEG_MAX) return hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-#define VLO_SEG_ATTR(K) (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        VLO_SEG_ATTR((attn_chunk_seg_kernel<128, 2>)); VLO_SEG_ATTR((attn_chunk_seg_kernel<128, 1>));
-        VLO_SEG_ATTR((attn_chunk_seg_kernel<64, 2>)); VLO_SEG_ATTR((attn_chunk_seg_kernel<64, 1>));
-        VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<128, 2>)); VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<128, 1>));
-        VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<64, 2>)); VLO_SEG_ATTR((attn_chunk_seg_f8_kernel<64, 1>));
-        VLO_SEG_ATTR((attn_cols_seg_kernel<128, 1>)); VLO_SEG_ATTR((attn_cols_seg_kernel<128, 2>)); VLO_SEG_ATTR((attn_cols_seg_kernel<128, 3>));
-        VLO_SEG_ATTR((attn_cols_seg_kernel<64, 1>)); VLO_SEG_ATTR((attn_cols_seg_kernel<64, 2>)); VLO_SEG_ATTR((attn_cols_seg_kernel<64, 3>));
-        VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 1>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 2>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<128, 3>));
-        VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 1>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 2>)); VLO_SEG_ATTR((attn_cols_seg_f8_kernel<64, 3>));
-#undef VLO_SEG_ATTR
-        (void)hipGetLastError();
-        attr_done = true;
-    }
     const KvGeom &kg = kv;
     for (int r = 0; r < nrun; ++r) {
         const AttnGeom &g = runs[r].g;
         const AttnSeg *sd = segs_dev + runs[r].first;
-        const dim3 grid(runs[r].max_nsplit, nkv, runs[r].count);
+        const dim3 grid(runs[r].max_nsplit, nkv, runs[r].count), block(g.nhg * g.KS * 64);
         const size_t lds = g.lds_bytes;
+        const AttnKernels *k = attn_kernels(hd, g.hpw, g.nct);
+        if (!k) return hipErrorInvalidValue;
         if (g.nct) {
-#define VLO_SEG_COLS(HD_, NCT_)                                                                                                          \
-    do {                                                                                                                                 \
-        if (f8) hipLaunchKernelGGL((attn_cols_seg_f8_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd,     \
-                                   g.scale, part_o, part_ml, kv.scale);                                                                  \
-        else hipLaunchKernelGGL((attn_cols_seg_kernel<HD_, NCT_>), grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd, g.scale,  \
-                                part_o, part_ml);                                                                                        \
-    } while (0)
-            if (hd == 128 && g.nct == 1) VLO_SEG_COLS(128, 1);
-            else if (hd == 128 && g.nct == 2) VLO_SEG_COLS(128, 2);
-            else if (hd == 128) VLO_SEG_COLS(128, 3);
-            else if (g.nct == 1) VLO_SEG_COLS(64, 1);
-            else if (g.nct == 2) VLO_SEG_COLS(64, 2);
-            else VLO_SEG_COLS(64, 3);
-#undef VLO_SEG_COLS
+            if (f8) hipLaunchKernelGGL(k->cols_seg_f8, grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd, g.scale, part_o, part_ml, kv.scale);
+            else hipLaunchKernelGGL(k->cols_seg, grid, dim3(512), lds, st, q, kg, layer, num_heads, g.G, sd, g.scale, part_o, part_ml);
         } else {
-            const dim3 block(g.nhg * g.KS * 64);
-#define VLO_SEG_CHUNK(HD_, HPW_)                                                                                                          \
-    do {                                                                                                                                  \
-        if (f8) hipLaunchKernelGGL((attn_chunk_seg_f8_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd,   \
-                                   g.scale, part_o, part_ml, kv.scale);                                                                   \
-        else hipLaunchKernelGGL((attn_chunk_seg_kernel<HD_, HPW_>), grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd, g.scale, \
-                                part_o, part_ml);                                                                                         \
-    } while (0)
-            if (hd == 128 && g.hpw == 2) VLO_SEG_CHUNK(128, 2);
-            else if (hd == 128 && g.hpw == 1) VLO_SEG_CHUNK(128, 1);
-            else if (hd == 64 && g.hpw == 2) VLO_SEG_CHUNK(64, 2);
-            else if (hd == 64 && g.hpw == 1) VLO_SEG_CHUNK(64, 1);
-            else return hipErrorInvalidValue;
-#undef VLO_SEG_CHUNK
+            if (f8) hipLaunchKernelGGL(k->chunk_seg_f8, grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd, g.scale, part_o, part_ml, kv.scale);
+            else hipLaunchKernelGGL(k->chunk_seg, grid, block, lds, st, q, kg, layer, num_heads, g.G, g.KS, sd, g.scale, part_o, part_ml);
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (hd == 128) hipLaunchKernelGGL(attn_combine_seg_kernel<128>, dim3(num_heads, 16, nseg), dim3(256), 0, st, part_o, part_ml, segs_dev, num_heads, out, (int)packed);
-    else if (hd == 64) hipLaunchKernelGGL(attn_combine_seg_kernel<64>, dim3(num_heads, 16, nseg), dim3(256), 0, st, part_o, part_ml, segs_dev, num_heads, out, (int)packed);
-    else return hipErrorInvalidValue;
+    const AttnCombine *c = attn_combine(hd);
+    if (!c) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(c->seg, dim3(num_heads, 16, nseg), dim3(256), 0, st, part_o, part_ml, segs_dev, num_heads, out, (int)packed);
     return hipGetLastError();
 }
 
