@@ -253,6 +253,19 @@ int vlo_logit_rows(vlo_engine *e, const void *logits_dev, int n, const int64_t *
 int vlo_session_fork(vlo_session *src, int64_t n_tokens, vlo_session **out, void *stream);
 /* in-place variant: forget every position >= n_tokens and return the freed pages to the pool (device-synchronising). */
 int vlo_session_crop(vlo_session *s, int64_t n_tokens);
+/* ---- bounded-context streams: forget cache positions [t0, t1) of the session (StreamingLLM's "positions within the cache": keep the
+ *      system prompt, drop the oldest frames).  Tokens [t1, len) move to [t0, len - d), d = t1 - t0, their keys re-rotated by -d positions
+ *      (rule below); len becomes len - d and whole pages freed at the tail return to the pool.  0 <= t0 <= t1 <= len; t0 == t1 is a no-op;
+ *      t1 == len is vlo_session_crop(t0) (nothing is rotated).  The session's last-row logits stay what they were.  Ordered on `stream`
+ *      behind the session's earlier work; pages are handed back only after the kernel has drained (device-synchronising then, as
+ *      vlo_session_crop).  kv_dtype = 1: VLO_E_UNSUPPORTED (every eviction would re-round the surviving keys to e4m3).
+ *      The re-rotation: with the engine's own inv_freq (fp32; a loaded "rope.inv_freq" included) the host computes, in double,
+ *      a_i = (double)d * (double)inv_freq[i], c_i = (float)cos(a_i), s_i = (float)sin(a_i), i < head_dim / 2 (they travel in the kernel
+ *      arguments; the bf16 cos / sin tables are not read).  Every moved key row becomes, in fp32 from the stored bf16 values, HF's
+ *      half-split pairing:  k'[i] = k[i] c_i + k[i + hd/2] s_i,  k'[i + hd/2] = k[i + hd/2] c_i - k[i] s_i,  each rounded ONCE to bf16
+ *      (nearest even).  V is moved bit for bit.  After the call `len` is again the next RoPE position, so positions never outgrow the
+ *      pool's tables however long the stream runs; a key that survives n evictions has been rounded n + 1 times. */
+int vlo_session_evict(vlo_session *s, int64_t t0, int64_t t1, void *stream);
 
 /* ---- tensor parallelism (north_star; new capability — the reference has none) -------------------
  * Engines created with vlo_config.tp_size = T > 1 / tp_rank = r hold rank r's shard (load_weight still takes the FULL
@@ -279,6 +292,7 @@ void vlo_tp_session_destroy(vlo_tp_session *t);
  * forked / cropped alike (vlo_session_fork / vlo_session_crop per shard); one process per GPU: every rank makes the same call */
 int  vlo_tp_session_fork(vlo_tp_session *src, int64_t n_tokens, vlo_tp_session **out, void *stream);
 int  vlo_tp_session_crop(vlo_tp_session *t, int64_t n_tokens);
+int  vlo_tp_session_evict(vlo_tp_session *t, int64_t t0, int64_t t1, void *stream);   /* vlo_session_evict on every local shard alike */
 int  vlo_tp_llm_step(vlo_tp_session *t, const void *embeds_dev, int n, void *last_logits_dev, void *all_logits_dev, void *stream);
 int  vlo_tp_stream_sample(vlo_tp_session *t, float threshold, int interval_id, int64_t *tok_dev, float *p_interval_dev, void *stream);
 int  vlo_tp_greedy_generate(vlo_tp_session *t, const void *embeds_dev, int m, int eos_token_id, int64_t *out_ids_dev, int max_new,

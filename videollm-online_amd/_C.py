@@ -40,7 +40,7 @@ EXPORTS = [
     "vlo_joint_embed", "vlo_logit_rows", "vlo_session_fork", "vlo_session_crop", "vlo_tp_selftest", "vlo_debug_gemm64_plan", "vlo_debug_pack64_elem",
     "vlo_step_input", "vlo_build_id", "vlo_frame_ingest", "vlo_frame_ingest_geometry", "vlo_test_gemv_fp8", "vlo_test_gemm_fp8", "vlo_tp_comm_info", "vlo_tp_allgather",
     "vlo_tp_p2p_export", "vlo_tp_p2p_enable", "vlo_tp_p2p_status", "vlo_debug_p2p_layout", "vlo_tp_bench_exchange",
-    "vlo_tp_session_fork", "vlo_tp_session_crop",
+    "vlo_tp_session_fork", "vlo_tp_session_crop", "vlo_session_evict", "vlo_tp_session_evict",
     "vlo_batch_create", "vlo_batch_destroy", "vlo_batch_step", "vlo_batch_stream_sample", "vlo_batch_greedy_generate",
 ]
 
@@ -126,6 +126,8 @@ def bind(L):
     L.vlo_tp_session_destroy.restype = None
     L.vlo_tp_session_fork.argtypes = [vp, i64, C.POINTER(vp), vp]
     L.vlo_tp_session_crop.argtypes = [vp, i64]
+    L.vlo_session_evict.argtypes = [vp, i64, i64, vp]
+    L.vlo_tp_session_evict.argtypes = [vp, i64, i64, vp]
     L.vlo_batch_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.vlo_batch_destroy.argtypes = [vp]
     L.vlo_batch_destroy.restype = None

@@ -69,6 +69,7 @@ struct vlo_engine {
     void *conn_x = nullptr, *conn_mid = nullptr, *conn_out = nullptr;   // connector scratch: 2 slots of 32 rows each (two encode branches may run concurrently)
     void *cos_tab = nullptr, *sin_tab = nullptr;
     int64_t max_positions = 0;
+    std::vector<float> inv_freq_h;               // the inv_freq the tables were built from (loaded "rope.inv_freq" or the powf() one): vlo_session_evict
 
     // paged KV pool (bf16, or one e4m3 byte per element when cfg.kv_dtype = 1)
     void *k_pool = nullptr, *vt_pool = nullptr;
@@ -192,4 +193,5 @@ void ingest_destroy(vlo_engine *e);
 int connector_run(vlo_engine *e, int slot, const void *feats_dev, int rows, void *out_dev, hipStream_t st);   // slot 0 / 1: scratch set
 int session_fork_shard(vlo_session *src, int64_t n_tokens, vlo_session **out, void *stream);   // one KV shard (engine.hip)
 int session_crop_shard(vlo_session *s, int64_t n_tokens);
+int session_evict_shard(vlo_session *s, int64_t t0, int64_t t1, void *stream);
 int vlo_fail(int code, const std::string &msg);   // sets the thread-local error string, returns code

@@ -377,6 +377,7 @@ int vlo_engine_finalize(vlo_engine *e) {
         } else {
             for (int i = 0; i < half; ++i) inv[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)hd);
         }
+        e->inv_freq_h = inv;
         e->pool_pages = (int)((c.kv_pool_tokens + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS);
         e->max_positions = (int64_t)e->pool_pages * VLO_PAGE_TOKENS;
         std::vector<unsigned short> ct((size_t)e->max_positions * half), st((size_t)e->max_positions * half);
@@ -1574,6 +1575,51 @@ int session_crop_shard(vlo_session *s, int64_t n_tokens) {
 int vlo_session_crop(vlo_session *s, int64_t n_tokens) {
     if (s && s->e->tp_size > 1) return fail(VLO_E_STATE, "a tensor-parallel shard is cropped through vlo_tp_session_crop");
     return session_crop_shard(s, n_tokens);
+}
+
+// eviction of ONE KV shard: positions [t0, t1) leave the cache, the tail moves down by d = t1 - t0 slots with its keys rotated back by d
+// positions (llm_ops.hip kv_evict_kernel), so `len` is again the next position and no step kernel changes
+int session_evict_shard(vlo_session *s, int64_t t0, int64_t t1, void *stream) {
+    if (!s) return fail(VLO_E_INVALID, "bad session_evict arguments");
+    vlo_engine *e = s->e;
+    if (e->cfg.kv_dtype != VLO_KV_BF16)
+        return fail(VLO_E_UNSUPPORTED, "session_evict: an fp8 KV pool is not re-rotated (every eviction would re-round the surviving keys to e4m3)");
+    if (t0 < 0 || t1 < t0 || t1 > s->len) return fail(VLO_E_INVALID, "bad session_evict arguments: need 0 <= t0 <= t1 <= len");
+    const int64_t d = t1 - t0;
+    if (d == 0) return VLO_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (t1 < s->len) {
+        const int half = e->head_dim / 2;
+        if (half > 64 || (int)e->inv_freq_h.size() != half) return fail(VLO_E_UNSUPPORTED, "session_evict: head_dim must be 64 or 128");
+        KvEvictRot rot{};
+        for (int i = 0; i < half; ++i) {
+            const double a = (double)d * (double)e->inv_freq_h[i];
+            rot.c[i] = (float)cos(a);
+            rot.s[i] = (float)sin(a);
+        }
+        const hipError_t he = kv_evict_launch(kv_geom(s), e->cfg.num_layers, t0, d, s->len, rot, (hipStream_t)stream);
+        if (he == hipErrorNotSupported) return fail(VLO_E_UNSUPPORTED, "session_evict: head_dim must be 64 or 128");
+        HIP_TRY(he);
+    }
+    const int64_t nl = s->len - d;
+    const size_t keep = (size_t)((nl + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS);
+    if (keep < s->pages.size()) {
+        // as session_crop_shard: the pages go back to the pool only after the move above (it reads them) and any queued kernel that still
+        // reads them have drained.  The page-table prefix that stays is unchanged: nothing to upload
+        HIP_TRY(hipDeviceSynchronize());
+        std::lock_guard<std::mutex> g(e->pool_mu);
+        while (s->pages.size() > keep) {
+            e->free_pages.push_back(s->pages.back());
+            s->pages.pop_back();
+        }
+    }
+    s->len = nl;                                 // has_logits stays: the last row's logits are still the last row's
+    return VLO_OK;
+}
+
+int vlo_session_evict(vlo_session *s, int64_t t0, int64_t t1, void *stream) {
+    if (s && s->e->tp_size > 1) return fail(VLO_E_STATE, "a tensor-parallel shard is evicted through vlo_tp_session_evict");
+    return session_evict_shard(s, t0, t1, stream);
 }
 
 // device scratch of the test / micro-benchmark entry points: freed on every return path

@@ -127,6 +127,11 @@ hipError_t joint_embed_launch(const unsigned short *table, const int64_t *ids, i
                               hipStream_t st);
 // copy `pages` whole KV pages (all layers, K and V^T) from the physical pages src_pt[i] to dst_pt[i] (device int arrays); the page's BYTES
 hipError_t kv_copy_pages_launch(const KvPool &kv, const int *src_pt, const int *dst_pt, int pages, int layers, hipStream_t st);
+// vlo_session_evict on a bf16 pool (head_dim 64 or 128): tokens [t0 + d, len) of every layer move down by d slots in place (0 <= t0, d >= 1,
+// t0 + d < len), K rotated back by d positions with rot = {(float)cos, (float)sin of (double)d * inv_freq[i]}, i < head_dim / 2 (kernel
+// arguments), V^T moved bit for bit.  Reads kv.page_table up to the page of token len - 1.
+struct KvEvictRot { float c[64], s[64]; };
+hipError_t kv_evict_launch(const KvPool &kv, int layers, int64_t t0, int64_t d, int64_t len, const KvEvictRot &rot, hipStream_t st);
 // per-row logit statistics, see llm_ops.hip
 hipError_t logit_rows_launch(const unsigned short *logits, int n, int V, int64_t ld, const int64_t *labels, int interval_id, float *lse,
                              int64_t *amax, float *label_logit, float *p_interval, int64_t *p_amax, hipStream_t st);

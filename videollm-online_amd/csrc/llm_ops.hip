@@ -836,6 +836,154 @@ hipError_t kv_copy_pages_launch(const KvPool &kv, const int *src_pt, const int *
     return hipGetLastError();
 }
 
+// vlo_session_evict: forget cache positions [t0, t0 + d) of a bf16 pool.  Tokens [t0 + d, len) move down by d slots IN PLACE, their keys
+// rotated back by d positions (rot = cos / sin of d * inv_freq, vlo.h), V^T shifted bit for bit along its token axis.
+// The move overlaps itself, so its order matters.  Data of different (layer, kv head, K | V^T) never meet, nor do different hd rows of V^T:
+// a block owns one such slice (grid.x: kvh K slices of whole token rows, then kvh * HD / 64 V^T slices of 64 hd rows; grid.y = layer) and walks
+// its destination tokens in ascending CHUNKS (K: 16384 / HD tokens, V^T: 128).  A chunk [a, b) reads tokens [a + d, b + d) (V^T: from the
+// aligned 8-token vector holding a + d on), d >= 1: nothing below a — so no chunk reads what an EARLIER chunk stored — but possibly its own
+// range: every thread loads all the chunk needs into registers, __syncthreads(), then stores.  The loads of chunk c + 1 start at b or above,
+// which the stores of chunk c ([a, b)) cannot touch: they are issued before those stores (the prefetch; one barrier per chunk).
+// A thread's 4 items of a chunk are fixed at compile time: 8 uint4 in flight per thread and set, no indexing by a run-time value.
+#define EVICT_K_ITEMS 4
+#define EVICT_V_ITEMS 4
+template <int HD>
+__global__ __launch_bounds__(256) void kv_evict_kernel(KvGeom kv, long long t0, long long d, long long len, KvEvictRot rot) {
+    constexpr int PT = VLO_PAGE_TOKENS;
+    const int tid = threadIdx.x;
+    const long long nl = len - d;                              // the new length: destination tokens are [t0, nl)
+    const size_t lay = (size_t)blockIdx.y * kv.layer_stride;
+    const int *__restrict__ pt = kv.page_table;
+    const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+    if ((int)blockIdx.x < kv.num_kv_heads) {
+        // ---- K: whole token rows of one kv head.  item = (token, 16-byte unit u): pairs (8u + k, 8u + k + HD / 2), k < 8
+        constexpr int U = HD / 16, CT = 256 * EVICT_K_ITEMS / U, TS = 256 / U;
+        const int u = tid % U, tl = tid / U;
+        float c[8], s[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { c[k] = rot.c[u * 8 + k]; s[k] = rot.s[u * 8 + k]; }
+        bf16_t *base = kv.k_pool + lay + (size_t)blockIdx.x * PT * HD + u * 8;
+        auto row = [&](long long t) { return base + (size_t)pt[t / PT] * kv.page_elems + (size_t)(t % PT) * HD; };
+        uint4 cl[EVICT_K_ITEMS], ch[EVICT_K_ITEMS], nxl[EVICT_K_ITEMS], nxh[EVICT_K_ITEMS];
+        auto load = [&](long long cs, uint4 *lo, uint4 *hi) {
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) {
+                const long long t = cs + tl + i * TS;
+                lo[i] = hi[i] = z4;
+                if (t >= t0 && t < nl) {
+                    const bf16_t *src = row(t + d);
+                    lo[i] = *reinterpret_cast<const uint4 *>(src);
+                    hi[i] = *reinterpret_cast<const uint4 *>(src + HD / 2);
+                }
+            }
+        };
+        long long cs = t0 / CT * CT;
+        load(cs, cl, ch);
+        for (; cs < nl; cs += CT) {
+            if (cs + CT < nl) load(cs + CT, nxl, nxh);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) {
+                const long long t = cs + tl + i * TS;
+                if (t >= t0 && t < nl) {
+                    const unsigned lw[4] = {cl[i].x, cl[i].y, cl[i].z, cl[i].w}, hw[4] = {ch[i].x, ch[i].y, ch[i].z, ch[i].w};
+                    unsigned ol[4], oh[4];
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        // k'[i] = k[i] c + k[i + hd/2] s ; k'[i + hd/2] = k[i + hd/2] c - k[i] s, evaluated as written: two rounded fp32 products and
+                        // one rounded sum, never contracted into a fused multiply-add (when the two terms cancel, the fused form differs from the stated
+                        // one by many bf16 ulps of the small result)
+#pragma clang fp contract(off)
+                        const float a0 = __uint_as_float(lw[w] << 16), a1 = __uint_as_float(lw[w] & 0xffff0000u);
+                        const float b0 = __uint_as_float(hw[w] << 16), b1 = __uint_as_float(hw[w] & 0xffff0000u);
+                        const float c0 = c[2 * w], c1 = c[2 * w + 1], s0 = s[2 * w], s1 = s[2 * w + 1];
+                        ol[w] = pack2bf(a0 * c0 + b0 * s0, a1 * c1 + b1 * s1);
+                        oh[w] = pack2bf(b0 * c0 - a0 * s0, b1 * c1 - a1 * s1);
+                    }
+                    bf16_t *dst = row(t);
+                    *reinterpret_cast<uint4 *>(dst) = make_uint4(ol[0], ol[1], ol[2], ol[3]);
+                    *reinterpret_cast<uint4 *>(dst + HD / 2) = make_uint4(oh[0], oh[1], oh[2], oh[3]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) { cl[i] = nxl[i]; ch[i] = nxh[i]; }
+        }
+        return;
+    }
+    // ---- V^T: 64 hd rows of one kv head; the token axis is contiguous, so the move is a shift by d ELEMENTS: a destination vector of 8
+    // tokens starting at g is elements [sh, sh + 8) of the two aligned source vectors A = (g + d) / 8 and A + 1, sh = d % 8 (a funnel shift)
+    const int vs = (int)blockIdx.x - kv.num_kv_heads;
+    const int head = vs / (HD / 64), r0 = vs % (HD / 64) * 64;
+    const int sh = (int)(d & 7);
+    constexpr int VR = 256 * EVICT_V_ITEMS / 64, CV = VR * 8;   // vectors per row and tokens of a chunk
+    bf16_t *base = kv.vt_pool + lay + ((size_t)head * HD + r0) * PT;
+    // address of the aligned vector with GLOBAL index A (tokens 8A .. 8A + 7) of row r
+    auto vec = [&](long long A, int r) { return reinterpret_cast<uint4 *>(base + (size_t)pt[A / (PT / 8)] * kv.page_elems + (size_t)r * PT) + A % (PT / 8); };
+    uint4 ca[EVICT_V_ITEMS], cb[EVICT_V_ITEMS], na[EVICT_V_ITEMS], nb[EVICT_V_ITEMS];
+    auto load = [&](long long cs, uint4 *a, uint4 *b) {
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) {
+            const int idx = tid + 256 * i;
+            const long long g = cs + (idx % VR) * 8;
+            a[i] = b[i] = z4;
+            if (g + 8 > t0 && g < nl) {                        // some destination token of the vector is moved: g + d < len
+                const long long A = (g + d) >> 3;
+                a[i] = *vec(A, idx / VR);
+                if (sh && (A + 1) * 8 < len) b[i] = *vec(A + 1, idx / VR);   // tokens >= len feed no moved element
+            }
+        }
+    };
+    long long cs = t0 / CV * CV;
+    load(cs, ca, cb);
+    for (; cs < nl; cs += CV) {
+        if (cs + CV < nl) load(cs + CV, na, nb);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) {
+            const int idx = tid + 256 * i;
+            const long long g = cs + (idx % VR) * 8;
+            if (g + 8 > t0 && g < nl) {
+                unsigned w[8] = {ca[i].x, ca[i].y, ca[i].z, ca[i].w, cb[i].x, cb[i].y, cb[i].z, cb[i].w};
+                if (sh & 4) {
+#pragma unroll
+                    for (int m = 0; m < 6; ++m) w[m] = w[m + 2];
+                }
+                if (sh & 2) {
+#pragma unroll
+                    for (int m = 0; m < 5; ++m) w[m] = w[m + 1];
+                }
+                if (sh & 1) {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) w[m] = (w[m] >> 16) | (w[m + 1] << 16);
+                }
+                uint4 *dst = vec(g >> 3, idx / VR);
+                if (g >= t0 && g + 8 <= nl) {
+                    *dst = make_uint4(w[0], w[1], w[2], w[3]);
+                } else {                                       // the vector holding t0 or the new end: only the moved tokens are written
+                    bf16_t *d16 = reinterpret_cast<bf16_t *>(dst);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (g + k >= t0 && g + k < nl) d16[k] = (bf16_t)(w[k >> 1] >> ((k & 1) * 16));
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) { ca[i] = na[i]; cb[i] = nb[i]; }
+    }
+}
+hipError_t kv_evict_launch(const KvPool &kv, int layers, int64_t t0, int64_t d, int64_t len, const KvEvictRot &rot, hipStream_t st) {
+    if (kv.dtype != VLO_KV_BF16) return hipErrorNotSupported;
+    if (t0 < 0 || d <= 0 || t0 + d >= len) return hipErrorInvalidValue;   // nothing to move is the caller's case
+    const KvGeom &g = kv;
+    if (kv.head_dim == 128)
+        hipLaunchKernelGGL(kv_evict_kernel<128>, dim3(kv.num_kv_heads * 3, layers), dim3(256), 0, st, g, (long long)t0, (long long)d, (long long)len, rot);
+    else if (kv.head_dim == 64)
+        hipLaunchKernelGGL(kv_evict_kernel<64>, dim3(kv.num_kv_heads * 2, layers), dim3(256), 0, st, g, (long long)t0, (long long)d, (long long)len, rot);
+    else
+        return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
 // Per-row statistics of a bf16 logits matrix [n][ld] (one block per row): everything stream_evaluate reads from the
 // logits (models/modeling_live.py:95-97, 107-112, 140-144) without materialising softmax rows:
 //   lse[r]          log sum exp (fp32)                  -> cross entropy = lse - label_logit

@@ -321,6 +321,16 @@ int vlo_tp_session_crop(vlo_tp_session *t, int64_t n_tokens) {
     }
     return VLO_OK;
 }
+int vlo_tp_session_evict(vlo_tp_session *t, int64_t t0, int64_t t1, void *stream) {
+    if (!t || t0 < 0 || t1 < t0 || t1 > vlo_tp_session_len(t)) return vlo_fail(VLO_E_INVALID, "bad tp_session_evict arguments: need 0 <= t0 <= t1 <= len");
+    for (vlo_session *s : t->ss)
+        if (s->e->cfg.kv_dtype != VLO_KV_BF16) return vlo_fail(VLO_E_UNSUPPORTED, "tp_session_evict: an fp8 KV pool is not re-rotated");
+    for (vlo_session *s : t->ss) {               // checked above: no shard fails on its arguments after another has moved
+        const int rc = session_evict_shard(s, t0, t1, stream);
+        if (rc) return rc;
+    }
+    return VLO_OK;
+}
 
 // ---- p2p exchange ------------------------------------------------------------------------------------------------
 // Every rank owns a MAILBOX in its own HBM, mapped by every peer (hipIpc across processes, plain pointers inside one):

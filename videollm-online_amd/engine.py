@@ -130,6 +130,11 @@ class Session:
         """Forget every position >= n_tokens in place."""
         _C.check(_C.lib().vlo_session_crop(self._h, n_tokens))
 
+    def evict(self, t0: int, t1: int, stream=None):
+        """Forget cache positions [t0, t1) in place: the tail moves down by t1 - t0 slots with its keys re-rotated by as many positions
+        (include/vlo.h vlo_session_evict), so the length is again the next position.  Ordered on ``stream``; bf16 KV pools only."""
+        _C.check(_C.lib().vlo_session_evict(self._h, t0, t1, _stream_handle(stream)))
+
     def read_kv(self, layer, which, kv_head, t0, t1):
         out = torch.empty(t1 - t0, self.engine.head_dim, dtype=torch.bfloat16, device=self.engine.device)
         _C.check(_C.lib().vlo_session_read_kv(self._h, layer, which, kv_head, t0, t1, _ptr(out), _stream_handle()))
@@ -514,6 +519,10 @@ class TpSession:
     def crop(self, n_tokens: int):
         """Forget every position >= n_tokens in place, on every local KV shard."""
         _C.check(_C.lib().vlo_tp_session_crop(self._h, n_tokens))
+
+    def evict(self, t0: int, t1: int, stream=None):
+        """Forget cache positions [t0, t1) in place on every local KV shard (vlo_session_evict per shard)."""
+        _C.check(_C.lib().vlo_tp_session_evict(self._h, t0, t1, _stream_handle(stream)))
 
 
 class TpGroup:

@@ -15,7 +15,7 @@ from dataclasses import dataclass, field
 import torch
 
 from .modeling_live import LiveModel, fast_greedy_generate
-from .trace import frame_event, response_event, stage
+from .trace import evict_event, frame_event, response_event, stage
 
 
 @dataclass
@@ -30,10 +30,57 @@ class StreamTokens:
     query_ids: dict = field(default_factory=dict)
 
 
+KV_PAGE_TOKENS = 256       # tokens of one KV page (csrc/llm_ops.h VLO_PAGE_TOKENS): the hysteresis of KvBudget
+
+
+class KvBudget:
+    """Holds a stream's KV cache inside ``budget`` tokens: keep the first ``sink`` positions (the system prompt), keep the recent
+    past, drop the oldest steps (StreamingLLM's rule; the engine re-rotates the surviving keys, include/vlo.h vlo_session_evict).
+
+    Host bookkeeping only.  ``note_step(L0, n)`` records every Llama step (cache length before, new tokens): what it appends past
+    the sink is one SPAN.  ``enforce(cache, stream)`` — after a step or a response — does nothing while ``len(cache) <= budget``;
+    else it pops whole oldest spans until the length is at most ``budget - KV_PAGE_TOKENS`` (one page of hysteresis: an eviction
+    moves the whole tail, so it should be rare), never the newest span, and issues ONE ``cache.evict(sink, sink + d, stream)``.
+    Returns (t0, t1) of the eviction or None."""
+
+    def __init__(self, budget: int, sink: int, max_span: int):
+        budget, sink = int(budget), int(sink)
+        if sink < 0:
+            raise ValueError(f"kv_sink must be >= 0, got {sink}")
+        if budget < sink + max_span + KV_PAGE_TOKENS:
+            raise ValueError(f"kv_budget = {budget} cannot hold the sink ({sink} tokens), one step ({max_span}) and one KV page "
+                             f"({KV_PAGE_TOKENS}): it must be at least {sink + max_span + KV_PAGE_TOKENS}")
+        self.budget, self.sink = budget, sink
+        self.spans = collections.deque()
+        self.evictions = 0
+
+    def clear(self):
+        self.spans.clear()
+
+    def note_step(self, L0: int, n: int):
+        span = L0 + n - max(L0, self.sink)
+        if span > 0:
+            self.spans.append(span)
+
+    def enforce(self, cache, stream=None):
+        L = len(cache)
+        if L <= self.budget:
+            return None
+        d = 0
+        while len(self.spans) > 1 and L - d > self.budget - KV_PAGE_TOKENS:
+            d += self.spans.popleft()
+        if d == 0:
+            return None
+        cache.evict(self.sink, self.sink + d, stream=stream)
+        self.evictions += 1
+        return self.sink, self.sink + d
+
+
 class LiveInfer:
     def __init__(self, model: LiveModel, tokens: StreamTokens | None = None, tokenizer=None, frame_fps: float = 2,
                  system_prompt: str = "", prefetch: bool = True, prefetch_frames: int = 2, schedule=None,
-                 max_new_tokens: int = 100, record: int = 65536, encode_stream=None):
+                 max_new_tokens: int = 100, record: int = 65536, encode_stream=None, kv_budget: int | None = None,
+                 kv_sink: int | None = None):
         self.model = model
         self.engine = model.engine
         self.tokenizer = tokenizer
@@ -83,6 +130,14 @@ class LiveInfer:
         self._stage = torch.empty(64 + self.frame_num_tokens, self.hidden_size, dtype=torch.bfloat16, device=dev)
         # event log for tests / the bench: bounded (a long-running session must not grow host memory), cleared by reset()
         self._record = max(0, int(record))
+        # bounded context (None = the reference's ever-growing cache, no eviction call is ever made): see KvBudget.  The KV pool must
+        # hold the budget plus the step or response that crosses it: the eviction runs AFTER that step
+        self._kv_budget = None
+        if kv_budget is not None:
+            longest_step = 1 + len(self._added_stream_prompt_ids) + self.frame_num_tokens   # [eos] + stream prompt + the frame
+            self._kv_budget = KvBudget(kv_budget, len(self._start_ids) if kv_sink is None else kv_sink, longest_step)
+        elif kv_sink is not None:
+            raise ValueError("kv_sink without kv_budget")
         self.past_key_values = None
         self.reset()
 
@@ -112,11 +167,24 @@ class LiveInfer:
         self.trace = collections.deque(maxlen=self._record or 1)       # trace.FrameEvent / trace.ResponseEvent, newest last
         self.step_log = collections.deque(maxlen=self._record or 1)    # (cache length before, new tokens) of the Llama steps
         self.steps_total = 0               # Llama steps executed since reset() (step_log keeps the newest `record` of them)
+        if self._kv_budget is not None:
+            self._kv_budget.clear()
 
     def _log_step(self, Lc, n):
         self.steps_total += 1
         if self._record:
             self.step_log.append((Lc, n))
+        if self._kv_budget is not None:
+            self._kv_budget.note_step(Lc, n)
+
+    def _enforce_kv_budget(self, video_time):
+        """After a step or a response: one eviction on the main stream when the cache is over its budget (KvBudget)."""
+        if self._kv_budget is None:
+            return
+        with stage("evict"):
+            ev = self._kv_budget.enforce(self.past_key_values, self._main)
+        if ev is not None and self._record:
+            self.trace.append(evict_event(video_time, ev[0], ev[1], len(self.past_key_values)))
 
     def drop_prefetched(self):
         """Forget frames encoded ahead and not yet queued: with a resident video they are simply encoded again when their time
@@ -239,6 +307,7 @@ class LiveInfer:
         self.last_ids = out[-1:]
         if self._record:
             self.trace.append(response_event(video_time, query, out))
+        self._enforce_kv_budget(video_time)
         if query:
             query = f"(Video Time = {video_time}s) User: {query}"
         if self.tokenizer is not None:
@@ -278,6 +347,7 @@ class LiveInfer:
                 self._encode_async(nxt, nxt + self.prefetch_frames)
             # 2. if the same time, response after frame at that time
             if self.query_queue and video_time >= self.query_queue[0][0]:
+                self._enforce_kv_budget(video_time)
                 video_time, query = self.query_queue.popleft()
                 return video_time, query
             # 3. if the next is frame but next is not interval, then response
@@ -294,6 +364,7 @@ class LiveInfer:
             if self._record:
                 # trace.FrameEvent: the sampler's own choice differs from the token used only under a schedule
                 self.trace.append(frame_event(video_time, tok, len(self.past_key_values), sampled))
+            self._enforce_kv_budget(video_time)
             if tok != self.frame_token_interval_id:
                 return video_time, None
         return None, None

@@ -6,10 +6,11 @@ Events are plain tuples (named: they compare equal to bare tuples of the same co
 
   frame event     one per sampler decision of ``_call_for_streaming`` (demo/inference.py:75-81)
   response event  one per ``_call_for_response`` (demo/inference.py:40-52)
+  evict event     one per KV eviction of a LiveInfer with a ``kv_budget`` (no counterpart in the reference: its cache only grows)
 """
 from typing import NamedTuple, Optional
 
-FRAME, RESPONSE = "frame", "response"
+FRAME, RESPONSE, EVICT = "frame", "response", "evict"
 
 
 class FrameEvent(NamedTuple):
@@ -27,8 +28,17 @@ class ResponseEvent(NamedTuple):
     output_ids: list      # greedy tokens, EOS included
 
 
+class EvictEvent(NamedTuple):
+    kind: str            # EVICT
+    video_time: float    # time of the frame / response after which the cache was over its budget
+    t0: int              # cache positions [t0, t1) were forgotten: t0 = the sink, t1 - t0 = whole oldest steps
+    t1: int
+    kv_len: int          # KV length after the eviction
+
+
 FRAME_FIELDS = FrameEvent._fields
 RESPONSE_FIELDS = ResponseEvent._fields
+EVICT_FIELDS = EvictEvent._fields
 
 
 def frame_event(video_time, token, kv_len, sampled=None) -> FrameEvent:
@@ -38,6 +48,10 @@ def frame_event(video_time, token, kv_len, sampled=None) -> FrameEvent:
 
 def response_event(video_time, query, output_ids) -> ResponseEvent:
     return ResponseEvent(RESPONSE, video_time, query, list(output_ids))
+
+
+def evict_event(video_time, t0, t1, kv_len) -> EvictEvent:
+    return EvictEvent(EVICT, video_time, int(t0), int(t1), int(kv_len))
 
 
 # ---- per-stage trace ranges (the reference's only instrument is the wall clock of demo/cli.py:31-38) ---------------------------
