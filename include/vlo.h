@@ -44,7 +44,11 @@ enum {
     VLO_E_UNSUPPORTED = -6  /* shape the kernels do not cover */
 };
 
-enum { VLO_DT_F32 = 0, VLO_DT_BF16 = 1, VLO_DT_F16 = 2, VLO_DT_FP8_E4M3 = 3 /* OCP e4m3fn, one byte per element */ };
+enum { VLO_DT_F32 = 0, VLO_DT_BF16 = 1, VLO_DT_F16 = 2, VLO_DT_FP8_E4M3 = 3 /* OCP e4m3fn, one byte per element */,
+       /* OCP MX e2m1 codes, two per byte: a matrix [N][K] is passed with its logical shape {N, K} and N*K/2 bytes; byte j of a row holds k = 2j in
+        * the low nibble and k = 2j + 1 in the high one; a code is sign bit 3, exponent bits 2:1, mantissa bit 0 (+-{0, 0.5, 1, 1.5, 2, 3, 4, 6}) */
+       VLO_DT_FP4_E2M1X2 = 4,
+       VLO_DT_E8M0 = 5 /* OCP MX scale byte e: 2^(e - 127) */ };
 
 typedef struct vlo_engine vlo_engine;
 typedef struct vlo_session vlo_session;
@@ -85,7 +89,13 @@ typedef struct vlo_config {
     /* storage of the streamed Llama projections (q/k/v/o, gate/up/down, lm_head): 0 = bf16; 1 = fp8 e4m3 with one fp32 scale
      * per output channel (BASELINE.json configs[4] "fp8 MFMA weights").  With 1, vlo_engine_load_weight takes those matrices as
      * VLO_DT_FP8_E4M3 [N][K] plus "<name>_scale" f32 [N] (W ~= q * scale[n]); activations and accumulation are unchanged, the KV cache
-     * follows kv_dtype below. */
+     * follows kv_dtype below.
+     * 2 = OCP MXFP4: e2m1 codes with one e8m0 scale per 32 elements along K (4.25 bits per weight), W[n][k] = e2m1(code[n][k]) *
+     * 2^(scale[n][k / 32] - 127), expanded to bf16 in registers exactly (W4A16; nothing is applied after the sum).  The seven decoder
+     * projections are then loaded as VLO_DT_FP4_E2M1X2 {N, K} plus "<name>_scale" VLO_DT_E8M0 [N][K / 32]; scale bytes outside [2, 254] are
+     * refused (255 is NaN; 0 and 1 would make 0.5 x scale a bf16 sub-normal); every K must be a multiple of 128.  "lm_head.weight" is taken
+     * either the same way or as VLO_DT_FP8_E4M3 + f32 "_scale" as with 1: what was loaded decides.  tp_size > 1 and prefill_act_dtype = 1
+     * are refused with 2. */
     int32_t weight_dtype;
     /* X operands of the LONG-INPUT projections (>= 256 new tokens: teacher-forced evaluation, a long first prompt) on an engine with
      * weight_dtype = 1: 0 = bf16 (the e4m3 image is expanded to bf16 per GEMM, bf16 MFMA: the arithmetic of the live step); 1 = every X row
@@ -226,6 +236,8 @@ double vlo_step_algorithmic_bytes(const vlo_engine *e, int64_t Lc, int n);
 int vlo_test_gemv(const void *x_dev, const void *W_dev, float *y_dev, int n, int N, int K, void *stream);
 /* the same through the fp8 e4m3 weight image: Wq_dev fp8 [N][K], scale_dev f32 [N]; y = (x @ Wq^T) * scale */
 int vlo_test_gemv_fp8(const void *x_dev, const void *Wq_dev, const float *scale_dev, float *y_dev, int n, int N, int K, void *stream);
+/* the same through the mxfp4 weight image: codes_dev e2m1 [N][K / 2] bytes, scale_dev e8m0 [N][K / 32]; y = x @ dequantised(W)^T; K % 128 == 0 */
+int vlo_test_gemv_mxfp4(const void *x_dev, const void *codes_dev, const void *scale_dev, float *y_dev, int n, int N, int K, void *stream);
 /* the long-input W8A8 GEMM of an engine with prefill_act_dtype = 1 (csrc/prefill.h): x bf16 [M][K] quantised per row to e4m3, multiplied with
  * Wq fp8 [N][K] on the native fp8 MFMA; y f32 [M][N] = (xq @ Wq^T) * scale[n] * xscale[m].  N, K multiples of 256.  Optional outputs: xq_dev
  * [M][K] e4m3 codes in the kernel's row order (prefill.h::vlo_fp8_row_pos), xscale_dev f32 [M]; iters > 0: *avg_us = the GEMM alone, timed. */
@@ -341,14 +353,15 @@ int vlo_profile_read(vlo_engine *e, int64_t *launches, double *total_ms, double 
 int vlo_profile_calibrate(vlo_engine *e, void *stream, double *empty_bracket_us);
 
 /* host-side planner of the weight-streaming GEMV (no GPU needed): for a reduction length K returns
- * out4 = {waves per block, fragments per wave per chunk, K chunks per wave, K slices across blocks}; < 0 if K is not covered */
+ * out4 = {waves per block, fragments per wave per chunk, K chunks per wave, K slices across blocks}; < 0 if K is not covered.
+ * allow_ksplit | 0x200 asks for the plan of the mxfp4 weight image (its own list; bf16 and fp8 share the plain one) */
 int vlo_debug_gemv_plan(int K, int allow_ksplit, int *out4);
 /* block path (csrc/prefill.hip): (NW, KF, KC) chosen for a K; element offset of (row < 64, k) in the packed-64 layout */
 int vlo_debug_gemm64_plan(int K, int *out3);
 int64_t vlo_debug_pack64_elem(int row, int k);
 
 /* micro-benchmark of the weight-streaming GEMV on synthetic data (tools/bench_gemv.py): `nbuf` distinct
- * packed weight images are cycled so the 256 MiB Infinity Cache cannot serve re-reads. */
+ * packed weight images are cycled so the 256 MiB Infinity Cache cannot serve re-reads.  epi | 0x100: the fp8 e4m3 image; epi | 0x200: mxfp4 */
 int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, double *avg_us);
 
 /* debugging aid for tests: copy an internal per-session activation buffer of the LAST chunk to dst_dev.

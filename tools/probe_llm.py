@@ -10,6 +10,8 @@ SHAPES = {
                        num_key_value_heads=8, vocab_size=128256, rope_theta=500000.0),
     "tinyllama-1.1b": dict(hidden_size=2048, intermediate_size=5632, num_hidden_layers=22, num_attention_heads=32,
                            num_key_value_heads=4, vocab_size=32000, rope_theta=10000.0),
+    "llama-3-70b": dict(hidden_size=8192, intermediate_size=28672, num_hidden_layers=80, num_attention_heads=64,
+                        num_key_value_heads=8, vocab_size=128256, rope_theta=500000.0),      # fp8 / mxfp4 weights on one GPU (probe_step.py)
 }
 
 

@@ -32,13 +32,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--iters", type=int, default=40)
-    ap.add_argument("--weight-dtype", default="bf16")
+    ap.add_argument("--weight-dtype", default="bf16", help="bf16, fp8 or mxfp4")
+    ap.add_argument("--layers", type=int, default=0, help="decoder layers (0 = the model's own): a shorter stack of the same layer shape")
     ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"))
     ap.add_argument("--lens", default="0,4096,12288", help="cache lengths to time at")
     ap.add_argument("--ns", default="1,11", help="new tokens per step")
     args = ap.parse_args()
     lens = [int(v) for v in args.lens.split(",")]
-    cfg = EngineConfig(**SHAPES[args.model], kv_pool_tokens=max(65536, max(lens) + 4096), weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
+    shape = dict(SHAPES[args.model], **({"num_hidden_layers": args.layers} if args.layers else {}))
+    cfg = EngineConfig(**shape, kv_pool_tokens=max(65536, max(lens) + 4096), weight_dtype=args.weight_dtype, kv_dtype=args.kv_dtype)
     eng = Engine(cfg)
     random_llm_weights_to_engine(eng, cfg)
     eng.finalize()

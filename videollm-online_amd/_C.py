@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvlo.so")
 
 VLO_ABI_VERSION = 4
-DT_F32, DT_BF16, DT_F16, DT_FP8_E4M3 = 0, 1, 2, 3
+DT_F32, DT_BF16, DT_F16, DT_FP8_E4M3, DT_FP4_E2M1X2, DT_E8M0 = 0, 1, 2, 3, 4, 5
 
 
 class VloConfig(C.Structure):
@@ -42,6 +42,7 @@ EXPORTS = [
     "vlo_tp_p2p_export", "vlo_tp_p2p_enable", "vlo_tp_p2p_status", "vlo_debug_p2p_layout", "vlo_tp_bench_exchange",
     "vlo_tp_session_fork", "vlo_tp_session_crop", "vlo_session_evict", "vlo_tp_session_evict",
     "vlo_batch_create", "vlo_batch_destroy", "vlo_batch_step", "vlo_batch_stream_sample", "vlo_batch_greedy_generate",
+    "vlo_test_gemv_mxfp4",
 ]
 
 
@@ -105,6 +106,7 @@ def bind(L):
     L.vlo_step_algorithmic_bytes.restype = C.c_double
     L.vlo_test_gemv.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.vlo_test_gemv_fp8.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.vlo_test_gemv_mxfp4.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.vlo_test_gemm_fp8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_double), vp]
     L.vlo_bench_gemv.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_double)]
     L.vlo_debug_read.argtypes = [vp, i32, vp, i64, vp]

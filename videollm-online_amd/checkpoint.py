@@ -108,6 +108,48 @@ def quantize_fp8_per_channel(W: torch.Tensor):
     return q.to(torch.float8_e4m3fn), scale                # exact: q already holds e4m3 values
 
 
+MXFP4_BLOCK = 32
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# (midpoint between codes c and c + 1 as fp32 bits, whether the tie goes up): ties go to the even code
+_E2M1_MIDPOINTS = ((0x3E800000, False), (0x3F400000, True), (0x3FA00000, False), (0x3FE00000, True), (0x40200000, False), (0x40600000, True),
+                   (0x40A00000, False))        # 0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5
+
+
+def quantize_mxfp4(W: torch.Tensor):
+    """OCP MXFP4 quantisation of a Linear weight [out, in] (include/vlo.h vlo_config.weight_dtype = 2): per block of 32 elements along `in`,
+    E = clamp(floor(log2(max|x|)) - 2, -125, 127) (the shared exponent minus e2m1's largest), scale byte = E + 127, code = the e2m1 value nearest
+    to clamp(x / 2^E, -6, 6), ties to the even code; an all-zero block gets scale byte 127 and codes 0.  Returns (codes uint8 [out, in / 2] with
+    element 2j in the low nibble of byte j — sign bit 3, exponent bits 2:1, mantissa bit 0 — and scale uint8 [out, in / 32]).
+    log2 comes from frexp and the rounding from integer compares on the fp32 bit patterns, so that every device quantises alike (see
+    round_to_e4m3)."""
+    N, K = W.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: in_features {K} is not a multiple of {MXFP4_BLOCK}")
+    x = W.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = x.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)                           # amax = m * 2^ex, m in [0.5, 1)  ->  floor(log2(amax)) = ex - 1
+    E = torch.where(amax > 0, (ex - 3).clamp(-125, 127), torch.zeros_like(ex))
+    y = torch.ldexp(x, -E[..., None]).clamp_(-6.0, 6.0)  # exact: a power-of-two scaling
+    bits = y.abs().contiguous().view(torch.int32)       # non-negative floats order like their bit patterns
+    code = torch.zeros_like(bits)
+    for mid, up in _E2M1_MIDPOINTS:
+        code += (bits >= mid) if up else (bits > mid)
+    code |= (y < 0).to(torch.int32) << 3
+    code = code.reshape(N, K).to(torch.uint8)
+    return code[:, 0::2] | (code[:, 1::2] << 4), (E + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """(codes uint8 [N, K / 2], scale uint8 [N, K / 32]) -> the fp32 weights [N, K] an mxfp4 engine multiplies by: e2m1(code) * 2^(scale - 127),
+    every one of them a bf16 value for scale bytes in [2, 254]."""
+    codes, scale = codes.view(torch.uint8), scale.view(torch.uint8)
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    c = torch.stack((codes & 15, codes >> 4), dim=-1).reshape(N, K).long()
+    lut = torch.tensor(_E2M1_VALUES + tuple(-v for v in _E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    v = lut[c].reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return torch.ldexp(v, (scale.to(torch.int32) - 127)[..., None]).reshape(N, K)
+
+
 def merge_lora(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: float) -> torch.Tensor:
     """W [out,in] + scale * B [out,r] @ A [r,in], accumulated in fp32, rounded once to bf16."""
     return (W.float() + scale * (B.float() @ A.float())).to(torch.bfloat16)

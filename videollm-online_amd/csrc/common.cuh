@@ -115,3 +115,43 @@ VLO_DEV unsigned fp8x4_quant(float a, float b, float c, float d, float s) {
     return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, lo, true);
 }
 VLO_DEV float fp8_to_f32(unsigned byte) { return __builtin_amdgcn_cvt_pk_f32_fp8((int)byte, false)[0]; }
+
+// OCP MXFP4 (vlo_config.weight_dtype = 2) -> bf16, exact.  A code is e2m1 (sign bit 3, exponent bits 2:1, mantissa bit 0: +-{0, 0.5, 1, 1.5,
+// 2, 3, 4, 6}), a block of 32 codes along K shares one e8m0 scale byte e8 (2^(e8 - 127), 2 <= e8 <= 254 checked at load): every product
+// code * scale is a bf16 value.  One dword = the 8 codes of one lane of one MFMA fragment (k ascending from the low nibble).
+// gfx950 converts two codes per VALU operation (v_cvt_scalef32_pk_bf16_fp4, scale = the float 2^(e8 - 127)); a compiler without the builtin
+// takes the integer arm, which gives the same bits: exponent field e8 + e - 1 (e8 - 1 for the sub-normal code 0.5), mantissa bit 6 = the
+// code's mantissa bit, infinity where the product passes bf16's largest binade (e8 >= 253 only).
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4)
+#define VLO_HAS_CVT_SCALE_FP4 1
+#endif
+#endif
+VLO_DEV unsigned fp4_to_bf16_bits(unsigned c, unsigned e8) {       // integer arm: one code -> bf16 bits
+    const unsigned e = (c >> 1) & 3u, m = c & 1u;
+    const unsigned ex = e ? e8 + e - 1u : e8 - 1u;
+    unsigned b = e ? ((ex << 7) | (m << 6)) : (m ? (ex << 7) : 0u);
+    if (ex >= 255u && (e | m)) b = 0x7f80u;
+    return b | ((c & 8u) << 12);
+}
+template <int B>
+VLO_DEV unsigned fp4x2_to_bf16x2(unsigned src, unsigned e8) {      // byte B of src: low nibble -> low half
+#ifdef VLO_HAS_CVT_SCALE_FP4
+    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(src, __uint_as_float(e8 << 23), B));
+#else
+    const unsigned by = (src >> (8 * B)) & 0xffu;
+    return fp4_to_bf16_bits(by & 15u, e8) | (fp4_to_bf16_bits(by >> 4, e8) << 16);
+#endif
+}
+VLO_DEV frag_ab fp4x8_to_bf16(unsigned codes, unsigned e8) {       // one fragment of a lane
+    return __builtin_bit_cast(frag_ab, make_uint4(fp4x2_to_bf16x2<0>(codes, e8), fp4x2_to_bf16x2<1>(codes, e8),
+                                                  fp4x2_to_bf16x2<2>(codes, e8), fp4x2_to_bf16x2<3>(codes, e8)));
+}
+// one 16-byte register of the mxfp4 image (gemv.hip) = four consecutive fragments; `sc` = their four scale bytes, fragment 0 in the low byte
+VLO_DEV void fp4x32_to_bf16(frag_ab raw, unsigned sc, frag_ab &f0, frag_ab &f1, frag_ab &f2, frag_ab &f3) {
+    const uint4 u = __builtin_bit_cast(uint4, raw);
+    f0 = fp4x8_to_bf16(u.x, sc & 0xffu);
+    f1 = fp4x8_to_bf16(u.y, (sc >> 8) & 0xffu);
+    f2 = fp4x8_to_bf16(u.z, (sc >> 16) & 0xffu);
+    f3 = fp4x8_to_bf16(u.w, sc >> 24);
+}

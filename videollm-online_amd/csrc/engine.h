@@ -23,8 +23,9 @@ struct PackedLinear {
     int N = 0, K = 0, NT = 0;
     int NT_gemm = 0;          // tiles the image is ALLOCATED (and zero-filled) for: NT rounded up to 16 where a GEMM reads whole 256-column tiles of a
                               // width that is not one (a TP rank's lm_head shard: 16 032 -> 16 128 columns); 0 = NT
-    int wq = 0;               // 1: Wp is the fp8 e4m3 image (gemv.hip) and wscale holds the per-output-channel scales
+    int wq = 0;               // 1: Wp is the fp8 e4m3 image (gemv.hip) and wscale holds the per-output-channel scales; 2: the mxfp4 image + wblk
     float *wscale = nullptr;  // fp32 [NT * 16], packed row order
+    unsigned *wblk = nullptr; // wq = 2: the e8m0 block scales, one dword per weight register and row: [NT][K / 128][16] (gemv.hip)
     GemvPlan plan{};
     Gemm64Plan plan64{};      // the 64-token block path over the same packed image (prefill.hip)
 };

@@ -66,7 +66,7 @@ __global__ void sum_partials_kernel(const float *P, int ksplit, int ld, float *y
     y[i] = s;
 }
 
-static size_t dt_size(int dt) { return dt == VLO_DT_F32 ? 4 : (dt == VLO_DT_FP8_E4M3 ? 1 : 2); }
+static size_t dt_size(int dt) { return dt == VLO_DT_F32 ? 4 : (dt == VLO_DT_FP8_E4M3 || dt == VLO_DT_E8M0 ? 1 : 2); }
 
 int dev_alloc(void **p, size_t bytes) {
     HIP_TRY(hipMalloc(p, bytes ? bytes : 16));
@@ -109,7 +109,7 @@ int vlo_engine_create(const vlo_config *cfg, int device, vlo_engine **out) {
         return fail(VLO_E_INVALID, "bad Llama dimensions");
     const int hd = cfg->hidden_size / cfg->num_heads;
     if (hd != 64 && hd != 128) return fail(VLO_E_UNSUPPORTED, "head_dim must be 64 or 128");
-    if (cfg->weight_dtype != 0 && cfg->weight_dtype != 1) return fail(VLO_E_INVALID, "weight_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
+    if (cfg->weight_dtype < 0 || cfg->weight_dtype > 2) return fail(VLO_E_INVALID, "weight_dtype must be 0 (bf16), 1 (fp8 e4m3) or 2 (mxfp4)");
     if (cfg->prefill_act_dtype != 0 && !(cfg->prefill_act_dtype == 1 && cfg->weight_dtype == 1))
         return fail(VLO_E_INVALID, "prefill_act_dtype must be 0 (bf16), or 1 (fp8 e4m3 per-row-scaled, native fp8 MFMA) on an engine with weight_dtype = 1");
     if (cfg->kv_dtype != VLO_KV_BF16 && cfg->kv_dtype != VLO_KV_FP8) return fail(VLO_E_INVALID, "kv_dtype must be 0 (bf16) or 1 (fp8 e4m3)");
@@ -121,6 +121,8 @@ int vlo_engine_create(const vlo_config *cfg, int device, vlo_engine **out) {
         if (cfg->num_kv_heads % T || cfg->num_heads % T || cfg->intermediate_size % (T * 32) || cfg->vocab_size % (T * 16))
             return fail(VLO_E_UNSUPPORTED, "tp_size must divide kv heads, heads, intermediate_size/32 and vocab_size/16");
         if (T > 8) return fail(VLO_E_UNSUPPORTED, "tp_size > 8");
+        if (cfg->weight_dtype == 2)
+            return fail(VLO_E_UNSUPPORTED, "weight_dtype = 2 (mxfp4) with tp_size > 1: the mxfp4 GEMV has no plans for the shards' reduction lengths");
     }
     HIP_TRY(hipSetDevice(device));
     vlo_engine *e = new vlo_engine();
@@ -179,11 +181,46 @@ int vlo_engine_load_weight(vlo_engine *e, const char *name, const void *data, in
     // storage dtype inside the engine: LLM + connector bf16; ViT matmul weights f16, the rest of the ViT f32
     int ddt = VLO_DT_BF16;
     if (n == "rope.inv_freq") ddt = VLO_DT_F32;
+    const bool streamed = n.rfind("vision.", 0) != 0 && n.rfind("connector.", 0) != 0 &&
+                          (name_is(n, "proj.weight") || n == "lm_head.weight" || name_is(n, "proj.weight_scale") || n == "lm_head.weight_scale");
+    if (dtype == VLO_DT_FP4_E2M1X2 || dtype == VLO_DT_E8M0) {
+        // mxfp4 storage of the streamed projections (vlo_config.weight_dtype = 2): e2m1 codes, two per byte, logical shape [N][K], and
+        // "<name>_scale" e8m0 [N][K / 32]; quantised by the caller, kept as given
+        if (e->cfg.weight_dtype != 2 || !streamed)
+            return fail(VLO_E_INVALID, n + ": mxfp4 codes / e8m0 scales are accepted for the Llama projections of an engine created with weight_dtype = 2");
+        if (name_is(n, "_scale") ? dtype != VLO_DT_E8M0 : dtype != VLO_DT_FP4_E2M1X2)
+            return fail(VLO_E_INVALID, n + ": expected e2m1 codes (VLO_DT_FP4_E2M1X2) and e8m0 scales (VLO_DT_E8M0)");
+        if (ndim != 2) return fail(VLO_E_INVALID, n + ": expected a matrix");
+        const size_t bytes = dtype == VLO_DT_E8M0 ? numel : numel / 2;
+        if (dtype == VLO_DT_FP4_E2M1X2 && (shape[1] & 31)) return fail(VLO_E_INVALID, n + ": K must be a multiple of the 32-element scale block");
+        if (dtype == VLO_DT_E8M0) {             // checked before anything is allocated (the source may be host or device memory).  255 = NaN;
+            std::vector<uint8_t> host(bytes);   // 0 and 1 would make the code 0.5 a bf16 sub-normal
+            HIP_TRY(hipMemcpy(host.data(), data, bytes, hipMemcpyDefault));
+            for (size_t i = 0; i < bytes; ++i)
+                if (host[i] < 2 || host[i] > 254)
+                    return fail(VLO_E_INVALID, n + ": e8m0 scale byte " + std::to_string((int)host[i]) + " outside [2, 254]");
+        }
+        void *dst = nullptr;
+        HIP_TRY(hipMalloc(&dst, bytes ? bytes : 16));
+        const hipError_t ce = hipMemcpy(dst, data, bytes, hipMemcpyDefault);
+        if (ce != hipSuccess) {
+            hipFree(dst);
+            HIP_TRY(ce);
+        }
+        auto it = e->raw.find(n);
+        if (it != e->raw.end()) hipFree(it->second.ptr);
+        RawTensor t;
+        t.ptr = dst;
+        t.dtype = dtype;
+        t.shape.assign(shape, shape + ndim);
+        e->raw[n] = t;
+        return VLO_OK;
+    }
     if (dtype == VLO_DT_FP8_E4M3 || name_is(n, "_scale")) {
-        // fp8 storage of the streamed projections (vlo_config.weight_dtype = 1): quantised by the caller, kept as given
-        const bool streamed = n.rfind("vision.", 0) != 0 && n.rfind("connector.", 0) != 0 &&
-                              (name_is(n, "proj.weight") || n == "lm_head.weight" || name_is(n, "proj.weight_scale") || n == "lm_head.weight_scale");
-        if (e->cfg.weight_dtype != 1 || !streamed)
+        // fp8 storage of the streamed projections (vlo_config.weight_dtype = 1): quantised by the caller, kept as given.  An mxfp4 engine takes
+        // its lm_head this way too (the output layer is usually kept at 8 bits)
+        const bool lm_head_of_fp4 = e->cfg.weight_dtype == 2 && (n == "lm_head.weight" || n == "lm_head.weight_scale");
+        if ((e->cfg.weight_dtype != 1 && !lm_head_of_fp4) || !streamed)
             return fail(VLO_E_INVALID, n + ": fp8 weights / scales are accepted for the Llama projections of an engine created with weight_dtype = 1");
         if (name_is(n, "_scale") ? dtype != VLO_DT_F32 : dtype != VLO_DT_FP8_E4M3) return fail(VLO_E_INVALID, n + ": expected fp8 e4m3 data and f32 scales");
         ddt = dtype;
@@ -238,6 +275,17 @@ static int pack_into(vlo_engine *e, const std::string &name, int Nfull, int Kful
     int rc = take(e, name, {Nfull, Kfull}, &t);
     if (rc) return rc;
     const int NT = half < 0 ? (N + 15) / 16 : (N + 7) / 8;
+    if (pl.wq == 2) {
+        RawTensor sc;
+        if (t.dtype != VLO_DT_FP4_E2M1X2)
+            return fail(VLO_E_INVALID, name + ": this engine streams mxfp4 weights (weight_dtype = 2): load it as VLO_DT_FP4_E2M1X2 with its e8m0 _scale");
+        if ((rc = take(e, name + "_scale", {Nfull, Kfull / 32}, &sc))) return rc;
+        if (sc.dtype != VLO_DT_E8M0) return fail(VLO_E_INVALID, name + "_scale: expected e8m0 block scales");
+        const uint8_t *src = (const uint8_t *)t.ptr + ((size_t)row0 * Kfull + col0) / 2;
+        const uint8_t *ssrc = (const uint8_t *)sc.ptr + ((size_t)row0 * Kfull + col0) / 32;
+        HIP_TRY(pack_weight_mxfp4_launch(src, ssrc, pl.Wp, pl.wblk, N, K, Kfull / 2, Kfull / 32, NT, tile_stride, tile_offset, half, 0));
+        return VLO_OK;
+    }
     if (pl.wq) {
         RawTensor sc;
         if (t.dtype != VLO_DT_FP8_E4M3) return fail(VLO_E_INVALID, name + ": this engine streams fp8 weights (weight_dtype = 1): load it as VLO_DT_FP8_E4M3 with its _scale");
@@ -252,17 +300,35 @@ static int pack_into(vlo_engine *e, const std::string &name, int Nfull, int Kful
     return VLO_OK;
 }
 
-static int make_linear(vlo_engine *e, PackedLinear *pl, int N, int K, bool allow_ksplit, bool fp8 = false, bool pad_for_gemm = false) {
+// wq = the image format (PackedLinear::wq): 0 bf16, 1 fp8 e4m3 + per-channel scales, 2 mxfp4 (codes + e8m0 block scales)
+static int make_linear(vlo_engine *e, PackedLinear *pl, int N, int K, bool allow_ksplit, int wq = 0, bool pad_for_gemm = false) {
+    const bool fp8 = wq == 1;
     pl->N = N;
     pl->K = K;
     pl->NT = (N + 15) / 16;
     pl->NT_gemm = pad_for_gemm ? (pl->NT + 15) & ~15 : pl->NT;
-    pl->wq = fp8 ? 1 : 0;
-    if (gemv_plan(K, allow_ksplit, &pl->plan)) return fail(VLO_E_UNSUPPORTED, "no GEMV plan for K=" + std::to_string(K));
+    pl->wq = wq;
+    if (gemv_plan(K, allow_ksplit, &pl->plan, wq))
+        return fail(VLO_E_UNSUPPORTED, std::string(wq == 2 ? "no mxfp4 GEMV plan for K=" : "no GEMV plan for K=") + std::to_string(K));
     if (fp8 && ((pl->plan.KF & 1) || !(pl->plan.NW == 8 || (pl->plan.NW == 4 && pl->plan.KF == 14)) || (K & 63)))      // (4 x 14: K = 1792, gemv.hip)
         return fail(VLO_E_UNSUPPORTED, "fp8 weight image needs an even fragment count per wave (K=" + std::to_string(K) + ")");
-    if (gemm64_plan(K, &pl->plan64, fp8))
+    if (gemm64_plan(K, &pl->plan64, wq))
         return fail(VLO_E_UNSUPPORTED, "no block-GEMM plan for K=" + std::to_string(K));
+    if (wq == 2) {                               // codes: half a byte per weight; scales: one byte per 32 weights, as dwords per (tile, 128 k, row)
+        if (K & 127) return fail(VLO_E_UNSUPPORTED, "mxfp4 weight image needs K % 128 == 0 (K=" + std::to_string(K) + ")");
+        const size_t cbytes = (size_t)pl->NT_gemm * 16 * K / 2, sbytes = (size_t)pl->NT_gemm * 16 * K / 32;
+        int rc = dev_alloc(&pl->Wp, cbytes);
+        if (rc) return rc;
+        e->owned.push_back(pl->Wp);
+        if ((rc = dev_alloc((void **)&pl->wblk, sbytes))) return rc;
+        e->owned.push_back(pl->wblk);
+        e->weight_bytes += (int64_t)(cbytes + sbytes);
+        if (pl->NT_gemm > pl->NT) {              // the pad tiles: zero codes, scale byte 127
+            HIP_TRY(hipMemset((char *)pl->Wp + (size_t)pl->NT * 16 * K / 2, 0, (size_t)(pl->NT_gemm - pl->NT) * 16 * K / 2));
+            HIP_TRY(hipMemset((char *)pl->wblk + (size_t)pl->NT * 16 * K / 32, 0x7f, (size_t)(pl->NT_gemm - pl->NT) * 16 * K / 32));
+        }
+        return VLO_OK;
+    }
     const size_t bytes = (size_t)pl->NT_gemm * 16 * K * (fp8 ? 1 : 2);
     int rc = dev_alloc(&pl->Wp, bytes);
     if (rc) return rc;
@@ -309,23 +375,25 @@ int vlo_engine_finalize(vlo_engine *e) {
     const int NqF = c.num_heads * hd, NkvF = c.num_kv_heads * hd;       // full projection widths
     const int Nq = e->nh_l * hd, Nkv = e->nkv_l * hd, Nqkv = Nq + 2 * Nkv;   // this rank's heads
     int rc;
-    const bool f8 = c.weight_dtype == 1;
+    const int wfmt = c.weight_dtype;                 // the image format of the seven decoder projections
     e->layers.resize(c.num_layers);
     for (int l = 0; l < c.num_layers; ++l) {
         LayerWeights &L = e->layers[l];
         const std::string p = "model.layers." + std::to_string(l) + ".";
-        if ((rc = make_linear(e, &L.qkv, Nqkv, H, false, f8))) return rc;
+        if ((rc = make_linear(e, &L.qkv, Nqkv, H, false, wfmt))) return rc;
         if ((rc = pack_into(e, p + "self_attn.q_proj.weight", NqF, H, r * Nq, Nq, 0, H, L.qkv, 1, 0))) return rc;
         if ((rc = pack_into(e, p + "self_attn.k_proj.weight", NkvF, H, r * Nkv, Nkv, 0, H, L.qkv, 1, Nq / 16))) return rc;
         if ((rc = pack_into(e, p + "self_attn.v_proj.weight", NkvF, H, r * Nkv, Nkv, 0, H, L.qkv, 1, (Nq + Nkv) / 16))) return rc;
-        if ((rc = make_linear(e, &L.o, H, Nq, e->tp_size > 1, f8))) return rc;          // TP: fp32 partial sums, all-reduced
+        if ((rc = make_linear(e, &L.o, H, Nq, e->tp_size > 1, wfmt))) return rc;          // TP: fp32 partial sums, all-reduced
         if ((rc = pack_into(e, p + "self_attn.o_proj.weight", H, NqF, 0, H, r * Nq, Nq, L.o, 1, 0))) return rc;
-        if ((rc = make_linear(e, &L.gate_up, 2 * I, H, false, f8))) return rc;       // SwiGLU epilogue needs whole K
+        if ((rc = make_linear(e, &L.gate_up, 2 * I, H, false, wfmt))) return rc;       // SwiGLU epilogue needs whole K
+        if (wfmt == 2 && L.gate_up.plan.KF > 16)      // (gemv.hip: no norm-on-load kernel at 28 fragments per chunk)
+            return fail(VLO_E_UNSUPPORTED, "no mxfp4 norm-on-load GEMV plan for K=" + std::to_string(H));
         if (I % 16) return fail(VLO_E_UNSUPPORTED, "intermediate_size (per rank) must be a multiple of 16");
         // gate and up share every tile (8 + 8 rows): I/8 single tiles, SwiGLU inside one tile
         if ((rc = pack_into(e, p + "mlp.gate_proj.weight", Ifull, H, r * I, I, 0, H, L.gate_up, 1, 0, 0))) return rc;
         if ((rc = pack_into(e, p + "mlp.up_proj.weight", Ifull, H, r * I, I, 0, H, L.gate_up, 1, 0, 1))) return rc;
-        if ((rc = make_linear(e, &L.down, H, I, true, f8))) return rc;
+        if ((rc = make_linear(e, &L.down, H, I, true, wfmt))) return rc;
         if ((rc = pack_into(e, p + "mlp.down_proj.weight", H, Ifull, 0, H, r * I, I, L.down, 1, 0))) return rc;
         if ((rc = take_vec(e, p + "input_layernorm.weight", H, &L.ln_in))) return rc;
         if ((rc = take_vec(e, p + "post_attention_layernorm.weight", H, &L.ln_post))) return rc;
@@ -339,7 +407,12 @@ int vlo_engine_finalize(vlo_engine *e) {
     if ((rc = take_vec(e, "model.norm.weight", H, &e->norm_w))) return rc;
     // a tensor-parallel rank's vocabulary shard is padded to whole 256-column GEMM tiles (Llama-3 at T = 8: 16 032 -> 16 128), so that every row's
     // logits of a long input take the GEMM path like every other projection (tp.hip::tp_prefill)
-    if ((rc = make_linear(e, &e->lm_head, e->V_l, H, false, f8, e->tp_size > 1))) return rc;
+    int lm_wq = wfmt;                                // an mxfp4 engine's lm_head: mxfp4 or fp8 per channel, whichever was loaded
+    if (wfmt == 2) {
+        auto it = e->raw.find("lm_head.weight");
+        if (it != e->raw.end() && it->second.dtype == VLO_DT_FP8_E4M3) lm_wq = 1;
+    }
+    if ((rc = make_linear(e, &e->lm_head, e->V_l, H, false, lm_wq, e->tp_size > 1))) return rc;
     if ((rc = pack_into(e, "lm_head.weight", c.vocab_size, H, r * e->V_l, e->V_l, 0, H, e->lm_head, 1, 0))) return rc;
     {   // embedding table stays row-major (gather), replicated on every rank
         RawTensor t;
@@ -437,6 +510,9 @@ double vlo_step_algorithmic_bytes(const vlo_engine *e, int64_t Lc, int n) {
     if (c.weight_dtype == 1) {      // fp8 image: one byte per weight + one fp32 scale per output channel
         const double rows_per_layer = (c.num_heads + 2.0 * c.num_kv_heads) * hd + H + 2.0 * I + H;
         W = W / 2.0 + (rows_per_layer * c.num_layers + c.vocab_size) * 4.0;
+    } else if (c.weight_dtype == 2) {   // mxfp4 image: half a byte per weight + one scale byte per 32; the lm_head as it was loaded
+        const double lm = (double)c.vocab_size * H;
+        W = per_layer * c.num_layers / 2.0 * (0.5 + 1.0 / 32.0) + (e->lm_head.wq == 1 ? lm + c.vocab_size * 4.0 : lm * (0.5 + 1.0 / 32.0));
     }
     const double kv = 2.0 * c.num_layers * c.num_kv_heads * hd * (c.kv_dtype == VLO_KV_FP8 ? 1.0 : 2.0);   // K + V bytes per token
     return W + kv * (double)(Lc + n) + kv * n + 2.0 * n * H * 2.0;
@@ -606,7 +682,8 @@ int vlo_profile_read(vlo_engine *e, int64_t *launches, double *total_ms, double 
     if (bytes_per_launch) {
         // gate+up weights [2I][H] bf16 streamed once + h [n<=16][H] in + act [n][I] out (n = 11 nominal)
         const double H = e->cfg.hidden_size, I = e->cfg.intermediate_size;
-        const double wbytes = e->cfg.weight_dtype == 1 ? 2.0 * I * H + 2.0 * I * 4.0 : 2.0 * I * H * 2.0;   // fp8: codes + fp32 scales
+        const double wbytes = e->cfg.weight_dtype == 2 ? 2.0 * I * H * (0.5 + 1.0 / 32.0)                    // mxfp4: codes + e8m0 block scales
+                              : e->cfg.weight_dtype == 1 ? 2.0 * I * H + 2.0 * I * 4.0 : 2.0 * I * H * 2.0;   // fp8: codes + fp32 scales
         *bytes_per_launch = wbytes + 11.0 * H * 2.0 + 11.0 * I * 2.0;
     }
     return VLO_OK;
@@ -644,7 +721,8 @@ GemvArgs gemv_args(const PackedLinear &pl, const unsigned short *x, int ldx, int
     GemvArgs a{};
     a.Wp = pl.Wp;
     a.wq = pl.wq;
-    a.wscale = pl.wscale;
+    if (pl.wq == 2) a.wblk = pl.wblk;
+    else a.wscale = pl.wscale;
     a.x = x;
     a.K = pl.K;
     a.ldx = ldx;
@@ -948,6 +1026,11 @@ int prefill_gemm(vlo_session *s, const unsigned short *X, const PackedLinear &pl
         if (rc2) return rc2;
         if (s->pf_wexp) hipFree(s->pf_wexp);                     // the superseded scratch: nothing reads it after the synchronise above
         s->pf_wexp = p; s->pf_wexp_bytes = need;
+    }
+    if (pl.wq == 2) {                                            // mxfp4: codes x block scales -> bf16, nothing left for the epilogue
+        HIP_TRY(expand_mxfp4_image_launch(pl.Wp, pl.wblk, s->pf_wexp, NTg, K, st));
+        HIP_TRY(llm_gemm_launch(X, s->pf_wexp, m, N, K, out, ldo, kind, st));
+        return VLO_OK;
     }
     HIP_TRY(expand_fp8_image_launch(pl.Wp, s->pf_wexp, NTg, K, st));
     HIP_TRY(llm_gemm_launch(X, s->pf_wexp, m, N, K, out, ldo, kind, st, pl.wscale));
@@ -1702,6 +1785,35 @@ int vlo_test_gemv_fp8(const void *x_dev, const void *Wq_dev, const float *scale_
     return VLO_OK;
 }
 
+int vlo_test_gemv_mxfp4(const void *x_dev, const void *codes_dev, const void *scale_dev, float *y_dev, int n, int N, int K, void *stream) {
+    if (!x_dev || !codes_dev || !scale_dev || !y_dev || n <= 0 || n > 16 || N <= 0 || (N & 3)) return fail(VLO_E_INVALID, "bad test_gemv_mxfp4 arguments");
+    hipStream_t st = (hipStream_t)stream;
+    GemvPlan plan;
+    const bool whole_k = getenv("VLO_TEST_GEMV_WHOLE_K") && atoi(getenv("VLO_TEST_GEMV_WHOLE_K"));
+    if ((K & 127) || gemv_plan(K, !whole_k, &plan, 2)) return fail(VLO_E_UNSUPPORTED, "no mxfp4 GEMV plan for K=" + std::to_string(K));
+    const int NT = (N + 15) / 16;
+    ScratchBufs sc;
+    void *Wp = nullptr, *Sp = nullptr, *xp = nullptr;
+    float *P = nullptr, *Y = nullptr;
+    HIP_TRY(sc.alloc(&Wp, (size_t)NT * 16 * K / 2));
+    HIP_TRY(sc.alloc(&Sp, (size_t)NT * 16 * K / 32));
+    HIP_TRY(sc.alloc(&xp, (size_t)32 * K * 2));
+    HIP_TRY(sc.alloc((void **)&P, (size_t)plan.ksplit * 16 * NT * 16 * 4));
+    HIP_TRY(sc.alloc((void **)&Y, (size_t)16 * NT * 16 * 4));
+    HIP_TRY(hipMemsetAsync(xp, 0, (size_t)32 * K * 2, st));
+    HIP_TRY(hipMemcpyAsync(xp, x_dev, (size_t)n * K * 2, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(pack_weight_mxfp4_launch(codes_dev, scale_dev, Wp, Sp, N, K, K / 2, K / 32, NT, 1, 0, -1, st));
+    GemvArgs a{};
+    a.Wp = Wp; a.wq = 2; a.wblk = (const unsigned *)Sp; a.x = (const unsigned short *)xp; a.out_f32 = P;
+    a.K = K; a.ldx = K; a.ldo = NT * 16; a.NT = NT; a.N_valid = N; a.n_rows = n;
+    HIP_TRY(gemv_launch(a, plan, XSRC_PLAIN, EPI_PARTIAL_F32, st));
+    hipLaunchKernelGGL(sum_partials_kernel, dim3((n * NT * 16 + 255) / 256), dim3(256), 0, st, P, plan.ksplit, NT * 16, Y, n, NT * 16);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(y_dev, (size_t)N * 4, Y, (size_t)NT * 16 * 4, (size_t)N * 4, n, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return VLO_OK;
+}
+
 int vlo_test_gemm_fp8(const void *x_dev, const void *Wq_dev, const float *scale_dev, float *y_dev, void *xq_dev, float *xscale_dev, int M, int N, int K,
                       int iters, double *avg_us, void *stream) {
     if (!x_dev || !Wq_dev || !scale_dev || !y_dev || M <= 0 || !llm_gemm_fp8_ok(N, K)) return fail(VLO_E_INVALID, "bad test_gemm_fp8 arguments (N, K multiples of 256)");
@@ -1740,12 +1852,14 @@ int vlo_test_gemm_fp8(const void *x_dev, const void *Wq_dev, const float *scale_
 
 int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, double *avg_us) {
     const int fp8 = (epi & 0x100) ? 1 : 0;          // bit 8 of `epi`: time the fp8 e4m3 weight image instead of the bf16 one
+    const int fp4 = (epi & 0x200) ? 1 : 0;          // bit 9: the mxfp4 image
     epi &= 0xff;
     if (N <= 0 || K <= 0 || n_rows <= 0 || n_rows > 16 || iters <= 0 || nbuf <= 0 || !avg_us) return fail(VLO_E_INVALID, "bad bench_gemv arguments");
     GemvPlan plan;
-    if (gemv_plan(K, epi == EPI_PARTIAL_F32, &plan)) return fail(VLO_E_UNSUPPORTED, "no GEMV plan for K");
+    if (fp8 && fp4) return fail(VLO_E_INVALID, "bench_gemv: one weight format at a time");
+    if (gemv_plan(K, epi == EPI_PARTIAL_F32, &plan, fp4 ? 2 : 0)) return fail(VLO_E_UNSUPPORTED, "no GEMV plan for K");
     const int NT = (N + 15) / 16;
-    const size_t wbytes = (size_t)NT * 16 * K * (fp8 ? 1 : 2);
+    const size_t wbytes = fp4 ? (size_t)NT * 16 * K / 2 : (size_t)NT * 16 * K * (fp8 ? 1 : 2);
     if (fp8 && ((plan.KF & 1) || plan.NW != 8)) return fail(VLO_E_UNSUPPORTED, "no fp8 GEMV for this K");
     ScratchBufs sc;
     std::vector<void *> Wp(nbuf, nullptr);
@@ -1777,6 +1891,11 @@ int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, doubl
         HIP_TRY(sc.alloc(&wsc, (size_t)NT * 16 * 4));
         HIP_TRY(hipMemset(wsc, 0x3c, (size_t)NT * 16 * 4));
         a.wq = 1; a.wscale = (const float *)wsc;
+    }
+    if (fp4) {                                       // codes 0x3c = {4, 1.5}; scale bytes 0x7c = 2^-3: every weight finite and small
+        HIP_TRY(sc.alloc(&wsc, (size_t)NT * 16 * K / 32));
+        HIP_TRY(hipMemset(wsc, 0x7c, (size_t)NT * 16 * K / 32));
+        a.wq = 2; a.wblk = (const unsigned *)wsc;
     }
     a.x = (const unsigned short *)x; a.out_f32 = (float *)o32; a.out_bf16 = (unsigned short *)o16;
     a.K = K; a.ldx = K; a.ldo = (epi == EPI_SWIGLU) ? NT * 8 : NT * 16; a.NT = NT; a.N_valid = N; a.n_rows = n_rows;   // SwiGLU: 8 output columns per tile
@@ -1827,7 +1946,8 @@ int64_t vlo_debug_pack64_elem(int row, int k) { return (row < 0 || row >= VLO_BL
 
 int vlo_debug_gemv_plan(int K, int allow_ksplit, int *out4) {
     GemvPlan p;
-    if (!out4 || gemv_plan(K, allow_ksplit != 0, &p)) return fail(VLO_E_UNSUPPORTED, "no GEMV plan for K=" + std::to_string(K));
+    const int wq = (allow_ksplit & 0x200) ? 2 : 0;       // bit 9 (as in vlo_bench_gemv's `epi`): the mxfp4 image's plan
+    if (!out4 || gemv_plan(K, (allow_ksplit & 0xff) != 0, &p, wq)) return fail(VLO_E_UNSUPPORTED, "no GEMV plan for K=" + std::to_string(K));
     out4[0] = p.NW; out4[1] = p.KF; out4[2] = p.KC; out4[3] = p.ksplit;
     return VLO_OK;
 }

@@ -33,8 +33,11 @@ enum {
 
 struct GemvArgs {
     const void *Wp;               // packed weights (see gemv.hip)
-    int wq;                       // 0: bf16 image;  1: fp8 e4m3 image + per-output-channel scales
-    const float *wscale;          // wq: fp32 [NT * 16] in packed row order (row r of tile t at t * 16 + r)
+    int wq;                       // 0: bf16 image;  1: fp8 e4m3 image + per-output-channel scales;  2: mxfp4 image + e8m0 block scales
+    union {
+        const float *wscale;      // wq = 1: fp32 [NT * 16] in packed row order (row r of tile t at t * 16 + r)
+        const unsigned *wblk;     // wq = 2: [NT][K / 128][16] dwords = the four e8m0 scale bytes of weight register (tile, kf4), row r (gemv.hip)
+    };
     const unsigned short *x;      // XSRC_PLAIN: bf16 [16][ldx];  XSRC_NORM: residual stream h, bf16 [16][ldx]
     union {
         float *out_f32;           // EPI_PARTIAL_F32
@@ -77,7 +80,8 @@ static_assert(sizeof(GemvArgs) <= 232, "GemvArgs grew: see the union above");
 
 struct GemvPlan { int NW, KF, KC, ksplit; };
 
-int gemv_plan(int K, bool allow_ksplit, GemvPlan *p);
+// wq = the image format (GemvArgs::wq): the mxfp4 image has its own (waves, fragments) list, the bf16 / fp8 plans do not depend on it
+int gemv_plan(int K, bool allow_ksplit, GemvPlan *p, int wq = 0);
 // grid.x the launch will use (= number of sq_out partial rows an EPI_RESID launch writes)
 int gemv_grid_x(const GemvArgs &a, const GemvPlan &p, int epi);
 hipError_t gemv_launch(GemvArgs a, const GemvPlan &p, int xsrc, int epi, hipStream_t st);
@@ -89,5 +93,9 @@ hipError_t gemv_prepare(GemvArgs *a, const GemvPlan &p, int epi, int *grid_x, in
 // fp8 e4m3 source [N_valid][K] (row stride ldw BYTES) + per-row scales -> fp8 image and scales in packed row order
 hipError_t pack_weight_fp8_launch(const void *W, const float *scale, void *Wp, float *scale_p, int N_valid, int K, int ldw, int NT,
                                   int tile_stride, int tile_offset, int half, hipStream_t st);
+// mxfp4: e2m1 codes [N_valid][K / 2] (two per byte, low nibble first; row stride ldw BYTES) + e8m0 scales [N_valid][K / 32] (row stride lds
+// bytes) -> the mxfp4 image and its scale dwords; K % 128 == 0.  Rows past N_valid: zero codes, scale byte 127
+hipError_t pack_weight_mxfp4_launch(const void *W, const void *scale, void *Wp, void *Sp, int N_valid, int K, int ldw, int lds, int NT,
+                                    int tile_stride, int tile_offset, int half, hipStream_t st);
 hipError_t pack_weight_launch(const void *W, void *Wp, int N_valid, int K, int ldw, int NT, int tile_stride, int tile_offset,
                               int half, hipStream_t st);

@@ -94,6 +94,43 @@ __global__ void pack_weight_fp8_kernel(const uint8_t *__restrict__ W, uint4 *__r
         Wp[((size_t)(tile * tile_stride + tile_offset) * KF2tot + kf2) * 64 + lane] = v;
     }
 }
+// mxfp4 image (vlo_config.weight_dtype = 2): OCP e2m1 codes, two per byte, and one e8m0 scale byte per 32 codes along K — 4.25 bits per weight,
+// still one 16-byte load per lane:
+//   Wp4[tile][kf4][lane] : 16 bytes = dword i (i = 0..3) = the 8 codes W[tile*16 + (lane&15)][(4*kf4 + i)*32 + (lane>>4)*8 .. +8], k ascending
+//                          from the low nibble
+// so one load feeds FOUR MFMAs.  A 32-element scale block of a row is exactly one fragment across the four lane quarters, so a lane needs one
+// scale byte per fragment = one dword per weight register, the same for the four lanes of a row.  The scales live in a parallel array in item order
+//   Sp4[tile][kf4][r] : dword = scale bytes of row tile*16 + r, fragments 4*kf4 .. 4*kf4 + 3 (fragment 4*kf4 in the low byte)
+// (64 bytes per KiB of codes, read by lane as r = lane & 15: no copy per quarter in HBM); its dword index is a quarter of the weight register's
+// uint4 index, and the loads ride the weight registers' rolling prefetch.  Codes x scale expand to bf16 in registers, exactly (common.cuh);
+// nothing is applied after the sum.
+__global__ void pack_weight_mxfp4_kernel(const uint8_t *__restrict__ W, const uint8_t *__restrict__ S, uint4 *__restrict__ Wp,
+                                         unsigned *__restrict__ Sp, int N_valid, int ldw, int lds, int NT, int KF4tot, int tile_stride,
+                                         int tile_offset, int half) {
+    const size_t total = (size_t)NT * KF4tot * 64;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(i & 63);
+        const size_t t = i >> 6;
+        const int kf4 = (int)(t % KF4tot);
+        const int tile = (int)(t / KF4tot);
+        const int r16 = lane & 15, qd = lane >> 4;
+        int n;
+        if (half < 0) n = tile * 16 + r16;
+        else if ((r16 >> 3) != half) continue;
+        else n = tile * 8 + (r16 & 7);
+        uint4 v = make_uint4(0, 0, 0, 0);
+        unsigned sc = 0x7f7f7f7fu;
+        if (n < N_valid) {
+            const uint8_t *row = W + (size_t)n * ldw + (size_t)kf4 * 64 + qd * 4;      // fragment f of the register: 16 bytes further each
+            v = make_uint4(*reinterpret_cast<const unsigned *>(row), *reinterpret_cast<const unsigned *>(row + 16),
+                           *reinterpret_cast<const unsigned *>(row + 32), *reinterpret_cast<const unsigned *>(row + 48));
+            sc = *reinterpret_cast<const unsigned *>(S + (size_t)n * lds + (size_t)kf4 * 4);
+        }
+        const size_t reg = (size_t)(tile * tile_stride + tile_offset) * KF4tot + kf4;
+        Wp[reg * 64 + lane] = v;
+        if (qd == 0) Sp[reg * 16 + r16] = sc;
+    }
+}
 __global__ void pack_scale_kernel(const float *__restrict__ scale, float *__restrict__ dst, int N_valid, int NT, int tile_stride,
                                   int tile_offset, int half) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -144,13 +181,29 @@ static int env_int(const char *name, int dflt) {
 }
 
 struct NwKf { int nw, kf; };
+// the mxfp4 image's own list (a weight register = four fragments: KF % 4 == 0).  K = 4096 / 8192: 8 x 16; 14336 / 28672: 8 x 28.
+// 1 x 4 is NOT a production plan: it exists so that the toy shapes of the CPU-emulation tests (K = 128 ... 1024) run at all, and it also catches
+// every other K = 128 j with j <= 16 (and 4 j <= 64 fragments in up to 16 chunks), e.g. a hidden size of 2048: correct, but one wave per block
+// keeps 1 KiB of codes in flight.  A model width that matters gets an (8, KF) entry here and its instantiations in launch_variant first.
+static const NwKf kCombosFp4[] = {{8, 16}, {8, 28}, {1, 4}};
 // (waves per block, fragments per wave per chunk) combinations that are instantiated, in preference order
 static const NwKf kCombos[] = {{8, 16}, {8, 14}, {8, 11}, {8, 8}, {8, 4}, {8, 2}, {8, 1}, {4, 14}, {4, 11}, {4, 1}, {2, 11}, {1, 1}};
 
-int gemv_plan(int K, bool allow_ksplit, GemvPlan *p) {
+int gemv_plan(int K, bool allow_ksplit, GemvPlan *p, int wq) {
     if (K <= 0 || (K & 31)) return -1;
     const int KFtot = K >> 5;
     const int force_ks = 0;
+    if (wq == 2) {                                   // the same rule over its own list: most bytes in flight per CU (K = 28672: 8 x 28, not 8 x 16)
+        const NwKf *best4 = nullptr;
+        for (const NwKf &c : kCombosFp4) {
+            if (KFtot % (c.nw * c.kf) || KFtot / (c.nw * c.kf) > 16) continue;
+            if (!best4 || c.nw * c.kf > best4->nw * best4->kf) best4 = &c;
+        }
+        if (!best4) return -1;
+        const int rest = KFtot / (best4->nw * best4->kf);
+        p->NW = best4->nw; p->KF = best4->kf; p->ksplit = allow_ksplit ? rest : 1; p->KC = rest / p->ksplit;
+        return 0;
+    }
     // the combination that keeps the most weight bytes in flight per CU (NW x KF KiB) wins, earlier entries on ties: every
     // model shape gets the same plan as a first-match walk of the list except K = 1792 (Llama-3-8B down-proj at TP = 8),
     // which would otherwise stream with 1 KiB per wave and seven K slices instead of 4 waves x 14 KiB and one
@@ -202,13 +255,29 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
     // 4 groups, 2 for the bf16 norm-on-load kernel (4 would spill: 16 + 16 fragment registers + the normalisation's temporaries).  Measured on the
     // 70B shapes (MI355X, profiles/r4_gemv_batch_loop.txt): fp8 gate/up 121.5 -> 87.9 us, qkv 26.2 -> 21.1, lm_head 184 -> 171; bf16 gate/up
     // 161.9 -> 155.4, qkv 36.6 -> 33.6; the bf16 lm_head (15.7 groups per block, the longest steady state) 313.6 -> 324.5: left on the group-outer loop
+    // mxfp4 image (a.wq == 2): the combinations of its own list (gemv_plan), four fragments per 16-byte load; every KC > 1 launch of 8 waves x 16 fragments
+    // takes the batch loop with 4 groups, lm_head included (a chunk's activation fragments are 4 x the bytes of an item's weights: re-reading them per
+    // group would dominate the stream).  Not built for it: the connector's GELU epilogue and the tensor-parallel mailbox epilogue (such engines are
+    // refused at create), and norm-on-load with 28 fragments per chunk (56 fragment registers + the codes' expansion: past the register file).
+    // 8 x 28 (K = 14336 / 28672, the down-proj) keeps the group-outer loop: its step launches split K across blocks (KC = 1), and 4 groups spill.
     static const int kBatch = env_int("VLO_GEMV_BATCH", 1);
 #define VLO_GO(XS, EP)                                                                            \
     do {                                                                                          \
         constexpr bool kHasBatch = (KF == 16 && NW == 8);                                         \
+        constexpr bool kFp4 = (NW == 8 && (KF == 16 || KF == 28)) || (NW == 1 && KF == 4);        \
+        constexpr bool kOld = !(NW == 8 && KF == 28) && !(NW == 1 && KF == 4);      /* combinations of the mxfp4 list alone */ \
         const bool batch = kHasBatch && kBatch && a.KC > 1 && (EP) != EPI_BF16_GELU_ERF; \
-        if (a.wq) {                                                                               \
-            if constexpr ((KF & 1) == 0 && (NW == 8 || (NW == 4 && KF == 14))) {    /* 4 x 14: K = 1792, the 8B down-proj shard at TP = 8 */ \
+        if (a.wq == 2) {                                                                          \
+            if constexpr (kFp4 && (EP) != EPI_BF16_GELU_ERF && (EP) != EPI_PARTIAL_MBOX && !((XS) == XSRC_NORM && KF > 16)) { \
+                if constexpr (kHasBatch) {                                                        \
+                    if (kBatch && a.KC > 1) { hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 2, 4>), grid, block, lds, st, a); return hipGetLastError(); } \
+                }                                                                                 \
+                hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 2>), grid, block, lds, st, a);  \
+            } else {                                                                              \
+                return hipErrorInvalidValue;                                                      \
+            }                                                                                     \
+        } else if (a.wq) {                                                                        \
+            if constexpr (kOld && (KF & 1) == 0 && (NW == 8 || (NW == 4 && KF == 14))) {    /* 4 x 14: K = 1792, the 8B down-proj shard at TP = 8 */ \
                 if constexpr (kHasBatch && (EP) != EPI_BF16_GELU_ERF) { \
                     if (batch) { hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 1, 4>), grid, block, lds, st, a); return hipGetLastError(); } \
                 }                                                                                 \
@@ -220,7 +289,8 @@ static hipError_t launch_variant(const GemvArgs &a, int xsrc, int epi, dim3 grid
             if constexpr (kHasBatch && (EP) != EPI_BF16_GELU_ERF && (EP) != EPI_BF16) {    \
                 if (batch) { hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 0, ((XS) == XSRC_NORM ? 2 : 4)>), grid, block, lds, st, a); return hipGetLastError(); } \
             }                                                                                     \
-            hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 0>), grid, block, lds, st, a);      \
+            if constexpr (kOld) hipLaunchKernelGGL((gemv16_kernel<KF, NW, XS, EP, 0>), grid, block, lds, st, a); \
+            else return hipErrorInvalidValue;                                                     \
         }                                                                                         \
         return hipGetLastError();                                                                 \
     } while (0)
@@ -268,6 +338,7 @@ hipError_t gemv_launch(GemvArgs a, const GemvPlan &p, int xsrc, int epi, hipStre
     if (p.NW == NW_ && p.KF == KF_) return launch_variant<KF_, NW_>(a, xsrc, epi, grid, lds, st);
     VLO_CASE(8, 16) VLO_CASE(8, 14) VLO_CASE(8, 11) VLO_CASE(8, 8) VLO_CASE(8, 4) VLO_CASE(8, 2) VLO_CASE(8, 1)
     VLO_CASE(4, 14) VLO_CASE(4, 11) VLO_CASE(4, 1) VLO_CASE(2, 11) VLO_CASE(1, 1)
+    VLO_CASE(8, 28) VLO_CASE(1, 4)             // mxfp4 only
 #undef VLO_CASE
     return hipErrorInvalidValue;
 }
@@ -283,6 +354,18 @@ hipError_t pack_weight_fp8_launch(const void *W, const float *scale, void *Wp, f
                        tile_stride, tile_offset, half);
     hipLaunchKernelGGL(pack_scale_kernel, dim3((NT * 16 + 255) / 256), dim3(256), 0, st, scale, scale_p, N_valid, NT, tile_stride,
                        tile_offset, half);
+    return hipGetLastError();
+}
+
+hipError_t pack_weight_mxfp4_launch(const void *W, const void *scale, void *Wp, void *Sp, int N_valid, int K, int ldw, int lds, int NT,
+                                    int tile_stride, int tile_offset, int half, hipStream_t st) {
+    if (K <= 0 || (K & 127) || (lds & 3) || (ldw & 3)) return hipErrorInvalidValue;
+    const int KF4tot = K >> 7;
+    const size_t total = (size_t)NT * KF4tot * 64;
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 65535) blocks = 65535;
+    hipLaunchKernelGGL(pack_weight_mxfp4_kernel, dim3(blocks), dim3(256), 0, st, (const uint8_t *)W, (const uint8_t *)scale, (uint4 *)Wp,
+                       (unsigned *)Sp, N_valid, ldw, lds, NT, KF4tot, tile_stride, tile_offset, half);
     return hipGetLastError();
 }
 

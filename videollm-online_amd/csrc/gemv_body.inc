@@ -88,7 +88,14 @@
                 // is re-loaded for the NEXT item right after the MFMA(s) that consumed it.  fp8 image: a register holds two fragments,
                 // expanded e4m3 -> bf16 (exact) in VALU slots the HBM-bound loop has to spare
                 auto mm = [&](f32x4 &acc, int i) {
-                    if (WQ) {
+                    if constexpr (WQ == 2) {
+                        frag_ab f0, f1, f2, f3;
+                        fp4x32_to_bf16(wr[i], sr[i], f0, f1, f2, f3);
+                        acc = mfma_bf16(f0, xf[4 * i], acc);
+                        acc = mfma_bf16(f1, xf[4 * i + 1], acc);
+                        acc = mfma_bf16(f2, xf[4 * i + 2], acc);
+                        acc = mfma_bf16(f3, xf[4 * i + 3], acc);
+                    } else if (WQ) {
                         frag_ab f0, f1;
                         fp8x16_to_bf16(wr[i], f0, f1);
                         acc = mfma_bf16(f0, xf[2 * i], acc);
@@ -103,6 +110,7 @@
                         for (int i = 0; i < WRN; ++i) {
                             mm(acc, i);
                             wr[i] = __builtin_nontemporal_load(np + i * 64);
+                            if constexpr (WQ == 2) sr[i] = __builtin_nontemporal_load(scale_ptr(np) + i * 16);
                         }
                     } else {
 #pragma unroll
@@ -120,7 +128,14 @@
         // batches of GB groups (g, g + GX, ...): chunk-outer, see the header.  Item order inside a batch: (c, j, A), (c, j, B) for
         // j = 0 .. GB-1, then chunk c + 1; the rolling prefetch follows that order across chunks and batches
         auto mm = [&](f32x4 &acc, int i) {
-            if (WQ) {
+            if constexpr (WQ == 2) {
+                frag_ab f0, f1, f2, f3;
+                fp4x32_to_bf16(wr[i], sr[i], f0, f1, f2, f3);
+                acc = mfma_bf16(f0, xf[4 * i], acc);
+                acc = mfma_bf16(f1, xf[4 * i + 1], acc);
+                acc = mfma_bf16(f2, xf[4 * i + 2], acc);
+                acc = mfma_bf16(f3, xf[4 * i + 3], acc);
+            } else if (WQ) {
                 frag_ab f0, f1;
                 fp8x16_to_bf16(wr[i], f0, f1);
                 acc = mfma_bf16(f0, xf[2 * i], acc);
@@ -135,6 +150,7 @@
                 for (int i = 0; i < WRN; ++i) {
                     mm(acc, i);
                     wr[i] = __builtin_nontemporal_load(np + i * 64);
+                    if constexpr (WQ == 2) sr[i] = __builtin_nontemporal_load(scale_ptr(np) + i * 16);
                 }
             } else {
 #pragma unroll

@@ -16,7 +16,7 @@
                     sA = f4add(sA, rb[(ww * CTG + 0) * 64 + l]);
                     sB = f4add(sB, rb[(ww * CTG + 1) * 64 + l]);
                 }
-                if (WQ) {                                  // per-output-channel weight scales (packed row order)
+                if (WQ == 1) {                             // per-output-channel weight scales (packed row order; the mxfp4 image carries its block scales in the stream)
                     sA = f4mul(sA, *reinterpret_cast<const float4 *>(a.wscale + tA * 16 + (l >> 4) * 4));
                     sB = f4mul(sB, *reinterpret_cast<const float4 *>(a.wscale + tB * 16 + (l >> 4) * 4));
                 }
@@ -100,14 +100,14 @@
                 const int m = l & 15;
                 const int col = tile * 16 + (l >> 4) * 4;
                 const bool live = (m < a.n_rows) && (tile < a.NT);
-                if (WQ && tile < a.NT) s = f4mul(s, *reinterpret_cast<const float4 *>(a.wscale + col));
+                if (WQ == 1 && tile < a.NT) s = f4mul(s, *reinterpret_cast<const float4 *>(a.wscale + col));
                 if (EPI == EPI_SWIGLU) {
                     // tile = 8 gate rows (fragment rows 0..7, lanes 0..31) + the 8 up rows of the same columns (lanes 32..63)
                     if (live && l < 32) {
                         float4 u = make_float4(0, 0, 0, 0);
 #pragma unroll
                         for (int ww = 0; ww < NW; ++ww) u = f4add(u, rb[(ww * CTG + ct) * 64 + l + 32]);
-                        if (WQ) u = f4mul(u, *reinterpret_cast<const float4 *>(a.wscale + col + 8));      // the tile's up rows
+                        if (WQ == 1) u = f4mul(u, *reinterpret_cast<const float4 *>(a.wscale + col + 8));      // the tile's up rows
                         const float gv[4] = {s.x, s.y, s.z, s.w}, uv[4] = {u.x, u.y, u.z, u.w};
                         bf16_t o[4];
 #pragma unroll

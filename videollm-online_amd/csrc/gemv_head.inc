@@ -2,6 +2,7 @@
 // fragments, which go in flight before anything else.
 // Expects in scope: template parameters KF, NW, XSRC, EPI, WQ; `GemvArgs a`; `float4 *red`; VLO_GEMV_BX / VLO_GEMV_BY.
 // WQ = 1: the weight image is fp8 e4m3 (see gemv.hip): one 16-byte lane load carries TWO MFMA fragments.
+// WQ = 2: mxfp4 (e2m1 codes + e8m0 block scales): one 16-byte lane load carries FOUR fragments, one dword of `a.wblk` their four scale bytes.
     constexpr int CTG = 2;
     float *scratch = reinterpret_cast<float *>(red + 2 * NW * CTG * 64);   // rs[16] | tmp[NW*4][16]
     float *rs_lds = scratch;
@@ -22,10 +23,14 @@
     auto tile_a = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
     auto tile_b = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
 
-    constexpr int WRN = WQ ? KF / 2 : KF;                      // 16-byte weight registers per chunk (KiB in flight per wave)
-    const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ ? kfw0 / 2 : kfw0) * 64 + lane;
-    const size_t tile_stride = (size_t)(WQ ? KFtot / 2 : KFtot) * 64;
+    constexpr int WRN = WQ == 2 ? KF / 4 : WQ ? KF / 2 : KF;                      // 16-byte weight registers per chunk (KiB in flight per wave)
+    const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ == 2 ? kfw0 / 4 : WQ ? kfw0 / 2 : kfw0) * 64 + lane;
+    const size_t tile_stride = (size_t)(WQ == 2 ? KFtot / 4 : WQ ? KFtot / 2 : KFtot) * 64;
     auto item_ptr = [&](int tile, int c) { return wbase + (size_t)tile * tile_stride + (size_t)c * WRN * 64; };
+    // mxfp4: the scale dwords of weight register (tile, kf4) are the 16 dwords (one per row of the tile) at (tile * KFtot / 4 + kf4) * 16, i.e. a
+    // quarter of the register's own offset: the scales of an item are found from the item's weight pointer and ride the same rolling prefetch
+    const unsigned *sbase = WQ == 2 ? a.wblk + (size_t)(kfw0 / 4) * 16 + m16 : nullptr;
+    auto scale_ptr = [&](const frag_ab *wp) { return sbase + ((wp - wbase) >> 2); };
 
     // ---- XSRC_NORM: the producer's row sums of squares head the kernel's only dependency chain (sums -> LDS -> barrier -> rsqrt -> normalised
     // activations -> first MFMA), so their loads go out FIRST — eight per thread cover sq_in_parts <= 8 * NW * 4 (256 producer blocks at 8 waves);
@@ -43,10 +48,15 @@
 
     // ---- first weight fragments go in flight right behind them -------------------------------
     frag_ab wr[WRN];
+    unsigned sr[WQ == 2 ? WRN : 1];           // mxfp4: the four e8m0 scale bytes of each weight register
     int g = VLO_GEMV_BX;                     // < ngroups: gemv_grid_x never launches more blocks than groups, so the loads below need no predicate
     {                                        // (a load behind a branch makes every wait that follows a vmcnt(0))
         const frag_ab *wp = item_ptr(tile_a(g), 0);
 #pragma unroll
         for (int kf = 0; kf < WRN; ++kf) wr[kf] = __builtin_nontemporal_load(wp + kf * 64);
+        if constexpr (WQ == 2) {
+#pragma unroll
+            for (int kf = 0; kf < WRN; ++kf) sr[kf] = __builtin_nontemporal_load(scale_ptr(wp) + kf * 16);
+        }
     }
 

@@ -7,7 +7,7 @@
 #define VLO_BLOCK_TOKENS 64      // token rows one weight pass of the block path covers (4 MFMA token tiles)
 
 struct Gemm64Plan { int NW, KF, KC; };
-int gemm64_plan(int K, Gemm64Plan *p, bool even_kf = false);     // even_kf: the fp8 image (two fragments per 16-byte register)
+int gemm64_plan(int K, Gemm64Plan *p, int wq = 0);     // wq = GemvArgs::wq: the fp8 image needs an even KF (two fragments per 16-byte register), mxfp4 KF % 4 == 0
 // y[m][n] = sum_k x[m][k] W[n][k] for up to 64 rows of x against the SAME packed weight image the 16-row GEMV streams
 // (gemv.hip; bf16, or fp8 e4m3 + scales when a.wq); epilogues EPI_BF16 / EPI_SWIGLU / EPI_RESID / EPI_ROPE with the rounding points of the GEMV path.
 // x is a PACKED-64 matrix (llm_ops.h::vlo_pack64_elem); EPI_SWIGLU also writes its output packed-64 (it feeds the down
@@ -35,6 +35,8 @@ hipError_t llm_gemm_launch(const unsigned short *X, const void *Wp, int M, int N
                            const float *wscale = nullptr);
 // fp8 e4m3 image Wp8[tile][kf2][lane] (gemv.hip) -> bf16 image Wp[tile][kf][lane], exact (every e4m3 value is a bf16 value); NT tiles of K
 hipError_t expand_fp8_image_launch(const void *Wp8, void *Wp_bf16, int NT, int K, hipStream_t st);
+// mxfp4 image Wp4[tile][kf4][lane] + its scale dwords Sp4[tile][kf4][16] (gemv.hip) -> bf16 image, exact; the GEMM then runs as for a bf16 engine
+hipError_t expand_mxfp4_image_launch(const void *Wp4, const void *Sp4, void *Wp_bf16, int NT, int K, hipStream_t st);
 // ---- native fp8 MFMA for the prefill GEMMs of an fp8 engine (vlo_config.prefill_act_dtype = 1; BASELINE.json configs[4] "fp8 MFMA weights") ----
 // W8A8: the X operand of a projection is quantised per ROW to OCP e4m3 — scale[m] = max|X[m]| * (1 / 448) (1 for a zero row), code =
 // e4m3_rne(clamp(X[m][k] / scale[m], -448, 448)), the weights' rule — and the GEMM multiplies e4m3 by e4m3 on v_mfma_f32_16x16x128_f8f6f4

@@ -19,6 +19,8 @@
 //
 // WQ = 1 streams the fp8 e4m3 image (gemv.hip: one 16-byte register = two consecutive fragments, expanded to bf16 exactly in
 // registers; per-output-channel scales on the reduced fp32 sums): one expansion feeds the four token tiles.
+// WQ = 2 streams the mxfp4 image (gemv.hip: one 16-byte register = four consecutive fragments, their e8m0 block scales one dword per register
+// from the parallel scale array; expanded to bf16 exactly in registers, nothing applied after the sum).
 #include <stdlib.h>
 
 #include "common.cuh"
@@ -30,8 +32,9 @@ VLO_DEV float4 f4add_p(float4 a, float4 b) { return make_float4(a.x + b.x, a.y +
 template <int KF, int EPI, int WQ>
 __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
     constexpr int MT = VLO_BLOCK_TOKENS / 16, CTG = 2;
-    constexpr int WRN = WQ ? KF / 2 : KF;                                  // weight registers per tile and K chunk (fp8: two fragments each)
+    constexpr int WRN = WQ == 2 ? KF / 4 : WQ ? KF / 2 : KF;               // weight registers per tile and K chunk (fp8: two fragments each, mxfp4: four)
     static_assert(!WQ || (KF % 2) == 0, "fp8 image: fragments come in pairs");
+    static_assert(WQ != 2 || (KF % 4) == 0, "mxfp4 image: fragments come in fours");
     extern __shared__ __attribute__((aligned(16))) float4 red[];          // [NW][CTG][MT][64] float4
     const int NW = blockDim.x >> 6;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -47,14 +50,18 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
     auto tile_a = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) : (single ? g : 2 * g); };
     auto tile_b = [&](int g) { return epi_rope(EPI) ? (g / hp) * tph + (g % hp) + hp : (single ? a.NT : 2 * g + 1); };
 
-    const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ ? kfw0 / 2 : kfw0) * 64 + lane;
-    const size_t tile_stride = (size_t)(WQ ? KFtot / 2 : KFtot) * 64;
+    const frag_ab *wbase = reinterpret_cast<const frag_ab *>(a.Wp) + (size_t)(WQ == 2 ? kfw0 / 4 : WQ ? kfw0 / 2 : kfw0) * 64 + lane;
+    const size_t tile_stride = (size_t)(WQ == 2 ? KFtot / 4 : WQ ? KFtot / 2 : KFtot) * 64;
     auto item_ptr = [&](int tile, int c) { return wbase + (size_t)tile * tile_stride + (size_t)c * WRN * 64; };
+    // mxfp4: a weight register's scale dword sits at a quarter of the register's own index, + the lane's row (gemv_head.inc)
+    const unsigned *sbase = WQ == 2 ? a.wblk + (size_t)(kfw0 / 4) * 16 + (lane & 15) : nullptr;
+    auto scale_ptr = [&](const frag_ab *wp) { return sbase + ((wp - wbase) >> 2); };
 
     // Weight fragments of BOTH tiles of the current K chunk sit in registers (2 x KF KiB per wave in flight) and each is
     // refilled for the next chunk right after the MFMAs that consumed it; the four activation fragments of step kf+1
     // are fetched (L2) while step kf computes.
     frag_ab wrA[WRN], wrB[WRN];
+    unsigned srA[WQ == 2 ? WRN : 1], srB[WQ == 2 ? WRN : 1];              // mxfp4: the registers' scale dwords
     frag_ab xc[MT], xn[MT];
     const frag_ab *xbase = reinterpret_cast<const frag_ab *>(a.x) + (size_t)kfw0 * MT * 64 + lane;   // packed-64 (llm_ops.h)
     auto load_x = [&](int step, frag_ab (&dst)[MT]) {                      // step = c * KF + kf inside this wave's K range
@@ -68,10 +75,18 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
         const int tb = tile_b(g);
 #pragma unroll
         for (int i = 0; i < WRN; ++i) wrA[i] = __builtin_nontemporal_load(pa + i * 64);
+        if constexpr (WQ == 2) {
+#pragma unroll
+            for (int i = 0; i < WRN; ++i) srA[i] = __builtin_nontemporal_load(scale_ptr(pa) + i * 16);
+        }
         if (tb < a.NT) {
             const frag_ab *pb = item_ptr(tb, 0);
 #pragma unroll
             for (int i = 0; i < WRN; ++i) wrB[i] = __builtin_nontemporal_load(pb + i * 64);
+            if constexpr (WQ == 2) {
+#pragma unroll
+                for (int i = 0; i < WRN; ++i) srB[i] = __builtin_nontemporal_load(scale_ptr(pb) + i * 16);
+            }
         }
         load_x(0, xc);
     }
@@ -91,25 +106,38 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
             const frag_ab *na = !last_c ? item_ptr(tA, c + 1) : (gn < ngroups ? item_ptr(tile_a(gn), 0) : nullptr);
             const int tBn = !last_c ? tB : (gn < ngroups ? tile_b(gn) : a.NT);
             const frag_ab *nb = tBn < a.NT ? item_ptr(tBn, last_c ? 0 : c + 1) : nullptr;
-            frag_ab eA[2], eB[2];                                          // fp8: the expanded fragment pair of the current register
+            frag_ab eA[WQ == 2 ? 4 : 2], eB[WQ == 2 ? 4 : 2];              // fp8 / mxfp4: the expanded fragments of the current register
 #pragma unroll
             for (int kf = 0; kf < KF; ++kf) {
                 // x of the next step (wraps to step 0 — same K range — when the next group starts)
                 const int nstep = (last_c && kf == KF - 1) ? 0 : c * KF + kf + 1;
                 load_x(nstep, xn);
-                if (WQ && !(kf & 1)) {                                     // expand, then the register is free for its refill
+                if constexpr (WQ == 2) {
+                    if (!(kf & 3)) {                                       // expand, then the register and its scales are free for their refill
+                        fp4x32_to_bf16(wrA[kf >> 2], srA[kf >> 2], eA[0], eA[1], eA[2], eA[3]);
+                        if (na) {
+                            wrA[kf >> 2] = __builtin_nontemporal_load(na + (kf >> 2) * 64);
+                            srA[kf >> 2] = __builtin_nontemporal_load(scale_ptr(na) + (kf >> 2) * 16);
+                        }
+                        if (hasB) fp4x32_to_bf16(wrB[kf >> 2], srB[kf >> 2], eB[0], eB[1], eB[2], eB[3]);
+                        if (nb) {
+                            wrB[kf >> 2] = __builtin_nontemporal_load(nb + (kf >> 2) * 64);
+                            srB[kf >> 2] = __builtin_nontemporal_load(scale_ptr(nb) + (kf >> 2) * 16);
+                        }
+                    }
+                } else if (WQ && !(kf & 1)) {                              // expand, then the register is free for its refill
                     fp8x16_to_bf16(wrA[kf >> 1], eA[0], eA[1]);
                     if (na) wrA[kf >> 1] = __builtin_nontemporal_load(na + (kf >> 1) * 64);
                     if (hasB) fp8x16_to_bf16(wrB[kf >> 1], eB[0], eB[1]);
                     if (nb) wrB[kf >> 1] = __builtin_nontemporal_load(nb + (kf >> 1) * 64);
                 }
-                const frag_ab fa = WQ ? eA[kf & 1] : wrA[kf];
+                const frag_ab fa = WQ == 2 ? eA[kf & 3] : WQ ? eA[kf & 1] : wrA[kf];
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
                     if (mt < mt_live) acc[0][mt] = mfma_bf16(fa, xc[mt], acc[0][mt]);
                 if (!WQ && na) wrA[kf] = __builtin_nontemporal_load(na + kf * 64);
                 if (hasB) {
-                    const frag_ab fb = WQ ? eB[kf & 1] : wrB[kf];
+                    const frag_ab fb = WQ == 2 ? eB[kf & 3] : WQ ? eB[kf & 1] : wrB[kf];
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
                         if (mt < mt_live) acc[1][mt] = mfma_bf16(fb, xc[mt], acc[1][mt]);
@@ -129,7 +157,7 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
         auto reduced = [&](int ct, int mt, int l) {
             float4 s = make_float4(0, 0, 0, 0);
             for (int ww = 0; ww < NW; ++ww) s = f4add_p(s, red[((size_t)(ww * CTG + ct) * MT + mt) * 64 + l]);
-            if (WQ) {                                                      // per-output-channel weight scales, packed row order (gemv.h)
+            if (WQ == 1) {                                                 // per-output-channel weight scales, packed row order (gemv.h)
                 const float4 sc = *reinterpret_cast<const float4 *>(a.wscale + (ct ? tB : tA) * 16 + (l >> 4) * 4);
                 s = make_float4(s.x * sc.x, s.y * sc.y, s.z * sc.z, s.w * sc.w);
             }
@@ -246,7 +274,7 @@ __global__ __launch_bounds__(512) void gemm64_kernel(GemvArgs a) {
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-int gemm64_plan(int K, Gemm64Plan *p, bool even_kf) {
+int gemm64_plan(int K, Gemm64Plan *p, int wq) {
     if (K <= 0 || (K & 31)) return -1;
     const int KFtot = K >> 5;
     // 8-wave blocks, one per CU, each wave keeping 2 x KF KiB of weight loads in flight (KF = 8: 128 KiB per CU, what the
@@ -254,7 +282,7 @@ int gemm64_plan(int K, Gemm64Plan *p, bool even_kf) {
     static const int nws[] = {8, 4, 2, 1}, kfs[] = {8, 4, 2, 1};
     for (int nw : nws)
         for (int kf : kfs)
-            if (KFtot % (nw * kf) == 0 && !(even_kf && (kf & 1))) {      // fp8 image: fragments are stored in pairs
+            if (KFtot % (nw * kf) == 0 && kf % (wq == 2 ? 4 : wq ? 2 : 1) == 0) {      // fp8 image: fragments are stored in pairs, mxfp4: in fours
                 p->NW = nw; p->KF = kf; p->KC = KFtot / (nw * kf);
                 return 0;
             }
@@ -297,6 +325,14 @@ hipError_t gemm64_launch(GemvArgs a, const Gemm64Plan &p, int epi, hipStream_t s
     gx = (ngroups + per - 1) / per;
     const size_t lds = (size_t)p.NW * 2 * (VLO_BLOCK_TOKENS / 16) * 64 * sizeof(float4);
     dim3 grid(gx), block(p.NW * 64);
+    if (a.wq == 2) {                             // mxfp4 image: four fragments per register
+        if (!a.wblk || (a.K & 127)) return hipErrorInvalidValue;
+        switch (p.KF) {
+            case 8: return launch64<8, 2>(a, epi, grid, block, lds, st);
+            case 4: return launch64<4, 2>(a, epi, grid, block, lds, st);
+        }
+        return hipErrorInvalidValue;
+    }
     if (a.wq) {                                  // fp8 image: fragment pairs
         if (!a.wscale || (a.K & 63)) return hipErrorInvalidValue;
         switch (p.KF) {
@@ -334,6 +370,27 @@ __global__ __launch_bounds__(256) void expand_fp8_image_kernel(const uint4 *__re
         d[0] = __builtin_bit_cast(uint4, f0);
         d[64] = __builtin_bit_cast(uint4, f1);
     }
+}
+// one 16-byte register of the mxfp4 image + its scale dword -> four 16-byte bf16 fragments
+__global__ __launch_bounds__(256) void expand_mxfp4_image_kernel(const uint4 *__restrict__ src, const unsigned *__restrict__ sc, uint4 *__restrict__ dst,
+                                                                 size_t n_regs) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_regs; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t lane = i & 63, reg = i >> 6;
+        frag_ab f0, f1, f2, f3;
+        fp4x32_to_bf16(__builtin_bit_cast(frag_ab, src[i]), sc[reg * 16 + (lane & 15)], f0, f1, f2, f3);
+        uint4 *d = dst + reg * 4 * 64 + lane;
+        d[0] = __builtin_bit_cast(uint4, f0);
+        d[64] = __builtin_bit_cast(uint4, f1);
+        d[128] = __builtin_bit_cast(uint4, f2);
+        d[192] = __builtin_bit_cast(uint4, f3);
+    }
+}
+hipError_t expand_mxfp4_image_launch(const void *Wp4, const void *Sp4, void *Wp_bf16, int NT, int K, hipStream_t st) {
+    if (!Wp4 || !Sp4 || !Wp_bf16 || NT <= 0 || K <= 0 || (K & 127)) return hipErrorInvalidValue;
+    const size_t n_regs = (size_t)NT * (K >> 7) * 64;
+    const int blocks = (int)std::min<size_t>((n_regs + 255) / 256, 4096);
+    hipLaunchKernelGGL(expand_mxfp4_image_kernel, dim3(blocks), dim3(256), 0, st, (const uint4 *)Wp4, (const unsigned *)Sp4, (uint4 *)Wp_bf16, n_regs);
+    return hipGetLastError();
 }
 hipError_t expand_fp8_image_launch(const void *Wp8, void *Wp_bf16, int NT, int K, hipStream_t st) {
     if (!Wp8 || !Wp_bf16 || NT <= 0 || (K & 63)) return hipErrorInvalidValue;

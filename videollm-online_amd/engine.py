@@ -11,6 +11,7 @@ from . import _C
 from .checkpoint import is_kv_scale
 
 _DT = {torch.float32: _C.DT_F32, torch.bfloat16: _C.DT_BF16, torch.float16: _C.DT_F16}
+_MX_DTYPES = tuple(getattr(torch, n) for n in ("float4_e2m1fn_x2", "float8_e8m0fnu") if hasattr(torch, n))
 
 
 @dataclass
@@ -35,7 +36,9 @@ class EngineConfig:
     tp_size: int = 1
     # storage of the streamed Llama projections: "bf16", or "fp8" = e4m3 + one fp32 scale per output channel
     # (BASELINE.json configs[4]; include/vlo.h vlo_config.weight_dtype).  bf16 weights handed to an fp8 engine are quantised
-    # on the way in (checkpoint.quantize_fp8_per_channel)
+    # on the way in (checkpoint.quantize_fp8_per_channel).  "mxfp4" = OCP MXFP4, e2m1 codes + one e8m0 scale per 32 elements along K
+    # (4.25 bits per weight, weight_dtype = 2): bf16 decoder projections are quantised on the way in (checkpoint.quantize_mxfp4), a bf16 lm_head
+    # goes to fp8 per channel; single GPU only
     weight_dtype: str = "bf16"
     # fp8 engines only: "fp8" = the long-input (prefill) projections quantise their X rows to e4m3 (one fp32 scale per row) and run on the native
     # fp8 MFMA (include/vlo.h vlo_config.prefill_act_dtype); "bf16" = expand the weight image per GEMM, bf16 MFMA.  The live step is bf16 either way.
@@ -55,9 +58,9 @@ class EngineConfig:
         c.pool_h, c.pool_w = self.frame_token_pooled
         c.kv_pool_tokens = self.kv_pool_tokens
         c.tp_rank, c.tp_size = self.tp_rank, self.tp_size
-        if self.weight_dtype not in ("bf16", "fp8"):
-            raise ValueError("weight_dtype must be 'bf16' or 'fp8'")
-        c.weight_dtype = 1 if self.weight_dtype == "fp8" else 0
+        if self.weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError("weight_dtype must be 'bf16', 'fp8' or 'mxfp4'")
+        c.weight_dtype = {"bf16": 0, "fp8": 1, "mxfp4": 2}[self.weight_dtype]
         if self.prefill_act_dtype not in ("bf16", "fp8") or (self.prefill_act_dtype == "fp8" and self.weight_dtype != "fp8"):
             raise ValueError("prefill_act_dtype must be 'bf16', or 'fp8' on an engine with weight_dtype='fp8'")
         c.prefill_act_dtype = 1 if self.prefill_act_dtype == "fp8" else 0
@@ -241,13 +244,31 @@ class Engine:
             self.load_weight(name, q)
             self.load_weight(name + "_scale", scale)
             return
+        if self.cfg.weight_dtype == "mxfp4" and streamed and t.is_floating_point() and t.dtype not in _MX_DTYPES + (torch.float8_e4m3fn,):
+            if name == "lm_head.weight":          # the output layer stays at 8 bits unless it is handed in as mxfp4
+                from .checkpoint import quantize_fp8_per_channel
+                q, scale = quantize_fp8_per_channel(t.to(self.device))
+            else:
+                from .checkpoint import quantize_mxfp4
+                q, scale = quantize_mxfp4(t.to(self.device))
+            self.load_weight(name, q)
+            self.load_weight(name + "_scale", scale)
+            return
+        shape = tuple(t.shape)
+        if t.dtype in _MX_DTYPES:                 # torch's own names for the two MX storage types: the same bytes
+            t = t.view(torch.uint8)
         if t.dtype == torch.float8_e4m3fn:
             dt, t = _C.DT_FP8_E4M3, t.view(torch.uint8)
+        elif t.dtype == torch.uint8:              # mxfp4, tagged by name: "<matrix>_scale" = e8m0 [N, K/32], the matrix = e2m1 codes [N, K/2]
+            if name.endswith("_scale"):
+                dt = _C.DT_E8M0
+            else:
+                dt, shape = _C.DT_FP4_E2M1X2, tuple(t.shape[:-1]) + (2 * t.shape[-1],)     # the C ABI takes the logical shape
         elif t.dtype in _DT:
             dt = _DT[t.dtype]
         else:
             raise TypeError(f"{name}: unsupported dtype {t.dtype}")
-        shape = (C.c_int64 * t.dim())(*t.shape)
+        shape = (C.c_int64 * len(shape))(*shape)
         _C.check(_C.lib().vlo_engine_load_weight(self._h, name.encode(), _ptr(t), dt, shape, t.dim()))
 
     def load_weights(self, weights: dict):
@@ -443,6 +464,16 @@ def test_gemv(x: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
     x, W = x.contiguous(), W.contiguous()
     y = torch.empty(x.shape[0], W.shape[0], dtype=torch.float32, device=x.device)
     _C.check(_C.lib().vlo_test_gemv(_ptr(x), _ptr(W), _ptr(y), x.shape[0], W.shape[0], W.shape[1], _stream_handle()))
+    return y
+
+
+def test_gemv_mxfp4(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """y[n,N] f32 = x[n,K] @ dequantize_mxfp4(codes [N,K/2], scale [N,K/32])^T through the mxfp4 weight image (unit tests)."""
+    x, codes, scale = x.contiguous(), codes.contiguous().view(torch.uint8), scale.contiguous().view(torch.uint8)
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    assert x.shape[1] == K and tuple(scale.shape) == (N, K // 32)
+    y = torch.empty(x.shape[0], N, dtype=torch.float32, device=x.device)
+    _C.check(_C.lib().vlo_test_gemv_mxfp4(_ptr(x), _ptr(codes), _ptr(scale), _ptr(y), x.shape[0], N, K, _stream_handle()))
     return y
 
 
