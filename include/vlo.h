@@ -225,6 +225,34 @@ int  vlo_batch_stream_sample(vlo_batch *b, float threshold, int interval_id, int
 int  vlo_batch_greedy_generate(vlo_batch *b, vlo_session *const *ss, int B, const void *embeds_dev, const int *m_host,
                                int eos_token_id, int64_t *out_ids_dev, int max_new, int *n_written_host, void *stream);
 
+/* ---- stream lookahead: a BACKLOG of frame steps of one session in one weight pass.  After a silent frame the sampled token is the interval
+ *      token (demo/inference.py:75-81), so the next step's input, [interval_id] + frame rows, is known before it runs: `units` queued step
+ *      inputs go through the decoder as ONE causal pass (a step streams the whole weight image whatever its row count), the streaming sampler
+ *      is evaluated at each unit's last row, and everything after the first unit that speaks is thrown away by the commit.
+ *      embeds_dev bf16 [n][hidden]: the rows of `units` consecutive step inputs; unit k ends at row unit_end_host[k] (strictly ascending, the
+ *      last entry n - 1).  1 <= units <= 16, 1 <= n <= 64: n <= 16 runs the 16-row pipeline, 17..64 the 64-row block path, so a unit's logits
+ *      equal those of vlo_llm_step over the SAME rows up to that unit's end only where both take the same path with the same row count (the
+ *      last unit always does; an earlier unit is inside the parity band, not bit-equal: profiles/stream_lookahead.md).  KV pages for len + n are
+ *      taken before anything is launched: when the pool cannot hold them the call fails and the session is unchanged.  Only the unit-end rows
+ *      take the final RMSNorm and the lm_head (one 16-row GEMV into the session's logits buffer [units][vocab]); each is sampled with
+ *      vlo_stream_sample's arithmetic and reduction order.  tok_dev int64 [units]; p_interval_dev NULL or f32 [units]; *n_accept_dev (int [1]) =
+ *      (smallest k with tok[k] != interval_id) + 1, or units when every unit stays silent.  Not for tensor-parallel engines (VLO_E_STATE).
+ *      Afterwards the session is PENDING: vlo_session_len still reports the old length, and every other call on the session returns
+ *      VLO_E_STATE except vlo_session_reset / vlo_session_destroy, which drop the pass. */
+int vlo_stream_steps(vlo_session *s, const void *embeds_dev, int n, const int *unit_end_host, int units, float threshold, int interval_id,
+                     int64_t *tok_dev, float *p_interval_dev, int *n_accept_dev, void *stream);
+/* keep the first keep_units (1..units) units of the pending pass: the length becomes len + unit_end[keep_units - 1] + 1 and the session's
+ *      last-row logits are that unit's (a following vlo_stream_sample reproduces tok[keep_units - 1] and p[keep_units - 1] bit for bit).  KV
+ *      pages that lie wholly behind the new length return to the pool as vlo_session_crop returns them (device-synchronising; no synchronise
+ *      when no page is freed); rows of discarded units inside kept pages stay as stale data behind `len`, as after a crop. */
+int vlo_stream_steps_commit(vlo_session *s, int keep_units);
+/* vlo_step_input for `units` (1..16) step inputs in ONE launch: unit u = the embeddings of its k_host[u] ids followed by frame rows
+ *      [u * rows_per_unit, (u + 1) * rows_per_unit) of frame_rows_dev (bf16 [units * rows_per_unit][hidden]).  ids_host: int64, the
+ *      concatenation of all units' ids, riding in the kernel arguments: at most 32 ids for unit 0 and at most 4 for each later unit.
+ *      out_dev: bf16 [sum k + units * rows_per_unit][hidden], bit-equal to `units` calls of vlo_step_input. */
+int vlo_steps_input(vlo_engine *e, const int64_t *ids_host, const int *k_host, int units, const void *frame_rows_dev, int rows_per_unit,
+                    void *out_dev, void *stream);
+
 /* ---- introspection for tests / bench ------------------------------------------------ */
 /* copy the session's K or V for (layer, kv_head) tokens [t0,t1) to dst_dev bf16 [t1-t0, head_dim] (kv_dtype = 1: bf16(code * scale)) */
 int vlo_session_read_kv(vlo_session *s, int layer, int which /*0=K,1=V*/, int kv_head, int64_t t0, int64_t t1,
@@ -366,7 +394,8 @@ int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, doubl
 
 /* debugging aid for tests: copy an internal per-session activation buffer of the LAST chunk to dst_dev.
  * which: 0 = q [16][nh*hd] bf16, 1 = attention output [16][nh*hd] bf16, 2 = residual stream h [16][H] bf16,
- *        3 = MLP activation [16][I] bf16, 4 = normed x [16][H] bf16 */
+ *        3 = MLP activation [16][I] bf16, 4 = normed x [16][H] bf16,
+ *        5 = the session's logits buffer [16][vocab] bf16 (after vlo_stream_steps + commit: row k = unit k of that pass, discarded units included) */
 int vlo_debug_read(vlo_session *s, int which, void *dst_dev, int64_t bytes, void *stream);
 
 const char *vlo_last_error(void);

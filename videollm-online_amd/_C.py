@@ -42,7 +42,7 @@ EXPORTS = [
     "vlo_tp_p2p_export", "vlo_tp_p2p_enable", "vlo_tp_p2p_status", "vlo_debug_p2p_layout", "vlo_tp_bench_exchange",
     "vlo_tp_session_fork", "vlo_tp_session_crop", "vlo_session_evict", "vlo_tp_session_evict",
     "vlo_batch_create", "vlo_batch_destroy", "vlo_batch_step", "vlo_batch_stream_sample", "vlo_batch_greedy_generate",
-    "vlo_test_gemv_mxfp4",
+    "vlo_test_gemv_mxfp4", "vlo_stream_steps", "vlo_stream_steps_commit", "vlo_steps_input",
 ]
 
 
@@ -95,6 +95,9 @@ def bind(L):
     L.vlo_connector.argtypes = [vp, vp, i32, vp, vp]
     L.vlo_embed.argtypes = [vp, vp, i32, vp, vp]
     L.vlo_step_input.argtypes = [vp, C.POINTER(i64), i32, vp, i32, vp, vp]
+    L.vlo_steps_input.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), i32, vp, i32, vp, vp]
+    L.vlo_stream_steps.argtypes = [vp, vp, i32, C.POINTER(i32), i32, C.c_float, i32, vp, vp, vp, vp]
+    L.vlo_stream_steps_commit.argtypes = [vp, i32]
     L.vlo_build_id.restype = C.c_char_p
     L.vlo_frame_ingest.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_float, vp, vp]
     L.vlo_frame_ingest_geometry.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]

@@ -124,6 +124,11 @@ struct vlo_session {
     float *partial_o = nullptr;                  // TP: o_proj partial sums [16][H] awaiting the all-reduce
     int64_t *tok = nullptr;
     float *sample_scratch = nullptr;
+    // stream lookahead (vlo_stream_steps): a pass of pend_units > 0 units has appended K / V behind `len` and awaits vlo_stream_steps_commit;
+    // until then `len` is the length before the pass, unit k ends at row pend_end[k] and `logits` holds the unit-end rows [pend_units][vocab]
+    int pend_units = 0;
+    int pend_end[VLO_ROWIDX_MAX] = {};
+    float *steps_scratch = nullptr;              // the rows sampler's scratch [VLO_ROWIDX_MAX][VLO_SAMPLE_SCRATCH_FLOATS]: allocated on first use
     int64_t *host_tok = nullptr;                 // pinned, 8 slots: tokens read back by the greedy loop (double-buffered)
     hipEvent_t tok_ev[2] = {nullptr, nullptr};   // "token i is on the host" (created on first use)
     int *page_table = nullptr, *host_pt = nullptr;

@@ -585,6 +585,7 @@ int vlo_session_reset(vlo_session *s) {
     s->pages.clear();
     s->len = 0;
     s->has_logits = false;
+    s->pend_units = 0;                           // a pending lookahead pass is dropped with its pages
     return VLO_OK;
 }
 int64_t vlo_session_len(const vlo_session *s) { return s ? s->len : -1; }
@@ -601,6 +602,12 @@ void vlo_session_destroy(vlo_session *s) {
     for (hipEvent_t ev : s->tok_ev) if (ev) hipEventDestroy(ev);
     if (s->host_pt) hipHostFree(s->host_pt);
     delete s;
+}
+
+// a session between vlo_stream_steps and vlo_stream_steps_commit takes no other call (reset and destroy drop the pending pass)
+static int pending_refusal(const vlo_session *s, const char *what) {
+    if (!s || !s->pend_units) return VLO_OK;
+    return fail(VLO_E_STATE, std::string(what) + ": a vlo_stream_steps pass is pending (call vlo_stream_steps_commit or vlo_session_reset)");
 }
 
 int ensure_pages(vlo_session *s, int64_t new_len, hipStream_t st) {
@@ -1102,6 +1109,7 @@ bool prefill_ok(const vlo_engine *e) {
 
 int vlo_llm_step(vlo_session *s, const void *embeds_dev, int n, void *last_logits_dev, void *all_logits_dev, void *stream) {
     if (!s || !embeds_dev || n <= 0) return fail(VLO_E_INVALID, "bad llm_step arguments");
+    if (int prc = pending_refusal(s, "llm_step")) return prc;
     vlo_engine *e = s->e;
     if (e->tp_size > 1) return fail(VLO_E_STATE, "tensor-parallel engine: step it through vlo_tp_llm_step");
     HIP_TRY(hipSetDevice(e->device));
@@ -1140,6 +1148,7 @@ int vlo_llm_step(vlo_session *s, const void *embeds_dev, int n, void *last_logit
 
 int vlo_stream_sample(vlo_session *s, float threshold, int interval_id, int64_t *tok_dev, float *p_interval_dev, void *stream) {
     if (!s || !tok_dev) return fail(VLO_E_INVALID, "bad stream_sample arguments");
+    if (int prc = pending_refusal(s, "stream_sample")) return prc;
     if (!s->has_logits) return fail(VLO_E_STATE, "no logits: call vlo_llm_step first");
     HIP_TRY(hipSetDevice(s->e->device));
     HIP_TRY(stream_sample_launch(s->last_logits, s->e->cfg.vocab_size, threshold, interval_id, tok_dev, p_interval_dev,
@@ -1177,9 +1186,102 @@ int vlo_step_input(vlo_engine *e, const int64_t *ids_host, int k, const void *fr
     return VLO_OK;
 }
 
+int vlo_steps_input(vlo_engine *e, const int64_t *ids_host, const int *k_host, int units, const void *frame_rows_dev, int rows_per_unit,
+                    void *out_dev, void *stream) {
+    if (!e || !out_dev || !k_host || units < 1 || units > VLO_STEPS_UNITS_MAX || rows_per_unit < 0 || (rows_per_unit > 0 && !frame_rows_dev))
+        return fail(VLO_E_INVALID, "bad steps_input arguments (1.." + std::to_string(VLO_STEPS_UNITS_MAX) + " units)");
+    if (!e->finalized) return fail(VLO_E_STATE, "engine not finalized");
+    StepsIds ids{};
+    for (int u = 0; u < units; ++u) {
+        const int k = k_host[u], kmax = u ? VLO_STEPS_IDS_LATER : VLO_STEP_IDS_MAX;
+        if (k < 0 || k > kmax || (k > 0 && !ids_host) || k + rows_per_unit < 1)
+            return fail(VLO_E_INVALID, "steps_input: unit " + std::to_string(u) + " carries " + std::to_string(k) + " ids (at most " + std::to_string(kmax) +
+                                           "; a unit has at least one row)");
+        for (int i = 0; i < k; ++i) ids.v[ids.id0[u] + i] = ids_host[ids.id0[u] + i];
+        ids.id0[u + 1] = ids.id0[u] + k;
+        ids.row0[u + 1] = ids.row0[u] + k + rows_per_unit;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(steps_input_launch((const unsigned short *)e->embed, ids, units, (const unsigned short *)frame_rows_dev, rows_per_unit, e->cfg.hidden_size,
+                               e->cfg.vocab_size, (unsigned short *)out_dev, (hipStream_t)stream));
+    return VLO_OK;
+}
+
+// ---- stream lookahead: a backlog of silent frame steps of ONE session in one weight pass -------------------------------------------------
+// After a silent frame the sampled token is the interval token, so the next step's input is known before it runs: `units` queued step inputs
+// go through the decoder as one causal pass of n rows (run_chunk's sequence up to 16 rows, run_block's above), only the unit-end rows take
+// the final norm and the lm_head (one 16-row GEMV: the head's weights are streamed once), and the rows sampler decides each.  The pass
+// leaves the session PENDING: its K / V lie behind `len`, the commit keeps the units up to the first that speaks and crops the rest.
+int vlo_stream_steps(vlo_session *s, const void *embeds_dev, int n, const int *unit_end_host, int units, float threshold, int interval_id,
+                     int64_t *tok_dev, float *p_interval_dev, int *n_accept_dev, void *stream) {
+    if (!s || !embeds_dev || !unit_end_host || !tok_dev || !n_accept_dev) return fail(VLO_E_INVALID, "bad stream_steps arguments");
+    vlo_engine *e = s->e;
+    if (e->tp_size > 1) return fail(VLO_E_STATE, "tensor-parallel engine: stream_steps is not supported");
+    if (int prc = pending_refusal(s, "stream_steps")) return prc;
+    if (units < 1 || units > VLO_ROWIDX_MAX) return fail(VLO_E_INVALID, "stream_steps: " + std::to_string(units) + " units (1.." + std::to_string(VLO_ROWIDX_MAX) + ")");
+    if (n < 1 || n > VLO_BLOCK_TOKENS) return fail(VLO_E_INVALID, "stream_steps: " + std::to_string(n) + " rows (1.." + std::to_string(VLO_BLOCK_TOKENS) + ")");
+    for (int k = 0; k < units; ++k)
+        if (unit_end_host[k] < (k ? unit_end_host[k - 1] + 1 : 0) || unit_end_host[k] >= n)
+            return fail(VLO_E_INVALID, "stream_steps: unit_end must be strictly ascending inside [0, n)");
+    if (unit_end_host[units - 1] != n - 1) return fail(VLO_E_INVALID, "stream_steps: the last unit must end at row n - 1");
+    const vlo_config &c = e->cfg;
+    const int H = c.hidden_size, V = c.vocab_size;
+    if (interval_id < 0 || interval_id >= V) return fail(VLO_E_INVALID, "stream_steps: interval_id outside the vocabulary");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    const bool block = n > 16;
+    int rc = 0;
+    if (block && (rc = ensure_block_ws(s))) return rc;
+    alloc_owned(rc, s->owned, &s->steps_scratch, (size_t)VLO_ROWIDX_MAX * VLO_SAMPLE_SCRATCH_FLOATS * 4);
+    if (rc) return rc;
+    if ((rc = ensure_pages(s, s->len + n, st))) return rc;          // all or nothing: a pool that cannot hold the pass leaves the session as it was
+    const StepWs &w = block ? s->bws : s->ws;
+    HIP_TRY(copy_rows_launch((const unsigned short *)embeds_dev, w.h, n, H, st));
+    PendingDown pd;
+    if ((rc = decoder_layers(e, w, n, block, solo_rows(s), false, st, &pd))) return rc;
+    // ---- the tail: final norm of the unit-end rows only (gathered into x rows 0 .. units - 1), one lm_head GEMV, the rows sampler
+    RowIdx rows{};
+    for (int k = 0; k < units; ++k) rows.v[k] = unit_end_host[k];
+    HIP_TRY(add_rmsnorm_gather_launch(w.h, pd.partial, pd.ksplit, H, (const unsigned short *)e->norm_w, w.x, H, c.rms_eps, rows, units, n, st));
+    GemvArgs a = gemv_args(e->lm_head, w.x, H, units);
+    a.out_bf16 = s->logits; a.ldo = V;
+    HIP_TRY(gemv_launch(a, e->lm_head.plan, XSRC_PLAIN, EPI_BF16, st));
+    HIP_TRY(stream_sample_steps_launch(s->logits, units, V, threshold, interval_id, tok_dev, p_interval_dev, n_accept_dev, s->steps_scratch, st));
+    s->has_logits = false;                       // the old last row's logits are overwritten; the commit names the new last row
+    s->pend_units = units;
+    for (int k = 0; k < units; ++k) s->pend_end[k] = unit_end_host[k];
+    return VLO_OK;
+}
+
+int vlo_stream_steps_commit(vlo_session *s, int keep_units) {
+    if (!s) return fail(VLO_E_INVALID, "null session");
+    if (!s->pend_units) return fail(VLO_E_STATE, "stream_steps_commit: no pass is pending");
+    if (keep_units < 1 || keep_units > s->pend_units)
+        return fail(VLO_E_INVALID, "stream_steps_commit: keep " + std::to_string(keep_units) + " of " + std::to_string(s->pend_units) + " units");
+    vlo_engine *e = s->e;
+    const int64_t nl = s->len + s->pend_end[keep_units - 1] + 1;
+    const size_t keep = (size_t)((nl + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS);
+    if (keep < s->pages.size()) {
+        // as session_crop_shard: pages wholly behind the kept units go back to the pool once the pass that wrote them has drained
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipDeviceSynchronize());
+        std::lock_guard<std::mutex> g(e->pool_mu);
+        while (s->pages.size() > keep) {
+            e->free_pages.push_back(s->pages.back());
+            s->pages.pop_back();
+        }
+    }
+    s->len = nl;
+    s->last_logits = s->logits + (size_t)(keep_units - 1) * e->cfg.vocab_size;
+    s->has_logits = true;
+    s->pend_units = 0;
+    return VLO_OK;
+}
+
 int vlo_greedy_generate(vlo_session *s, const void *embeds_dev, int m, int eos_token_id, int64_t *out_ids_dev, int max_new,
                         int force_len, int *n_written, void *stream) {
     if (!s || !embeds_dev || !out_ids_dev || m <= 0 || max_new <= 0) return fail(VLO_E_INVALID, "bad greedy_generate arguments");
+    if (int prc = pending_refusal(s, "greedy_generate")) return prc;
     vlo_engine *e = s->e;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1310,6 +1412,7 @@ static int batch_check(const vlo_batch *b, vlo_session *const *ss, int B, const 
     for (int i = 0; i < B; ++i) {
         if (!ss[i]) return fail(VLO_E_INVALID, "null session " + std::to_string(i));
         if (ss[i]->e != b->e) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " belongs to another engine");
+        if (int prc = pending_refusal(ss[i], "batched step")) return prc;
         for (int j = 0; j < i; ++j)
             if (ss[j] == ss[i]) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " repeats session " + std::to_string(j));
         if (n[i] < 1) return fail(VLO_E_INVALID, "session " + std::to_string(i) + " appends " + std::to_string(n[i]) + " tokens (>= 1)");
@@ -1567,6 +1670,7 @@ int vlo_session_read_kv(vlo_session *s, int layer, int which, int kv_head, int64
     if (!s || !dst_dev || layer < 0 || layer >= s->e->cfg.num_layers || kv_head < 0 || kv_head >= s->e->nkv_l ||
         t0 < 0 || t1 > s->len || t1 < t0)
         return fail(VLO_E_INVALID, "bad read_kv arguments");
+    if (int prc = pending_refusal(s, "read_kv")) return prc;
     HIP_TRY(hipSetDevice(s->e->device));
     HIP_TRY(read_kv_launch(kv_geom(s), layer, which, kv_head, t0, t1, (unsigned short *)dst_dev, (hipStream_t)stream));
     return VLO_OK;
@@ -1611,6 +1715,7 @@ int vlo_logit_rows(vlo_engine *e, const void *logits_dev, int n, const int64_t *
 // fork / crop of ONE KV shard (a whole TP = 1 session, or one rank's shard of a tensor-parallel session: tp.hip)
 int session_fork_shard(vlo_session *src, int64_t n_tokens, vlo_session **out, void *stream) {
     if (!src || !out || n_tokens < 0 || n_tokens > src->len) return fail(VLO_E_INVALID, "bad session_fork arguments");
+    if (int prc = pending_refusal(src, "session_fork")) return prc;
     vlo_engine *e = src->e;
     hipStream_t st = (hipStream_t)stream;
     vlo_session *d = nullptr;
@@ -1638,6 +1743,7 @@ int vlo_session_fork(vlo_session *src, int64_t n_tokens, vlo_session **out, void
 
 int session_crop_shard(vlo_session *s, int64_t n_tokens) {
     if (!s || n_tokens < 0 || n_tokens > s->len) return fail(VLO_E_INVALID, "bad session_crop arguments");
+    if (int prc = pending_refusal(s, "session_crop")) return prc;
     vlo_engine *e = s->e;
     const size_t keep = (size_t)((n_tokens + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS);
     if (keep < s->pages.size()) {
@@ -1664,6 +1770,7 @@ int vlo_session_crop(vlo_session *s, int64_t n_tokens) {
 // positions (llm_ops.hip kv_evict_kernel), so `len` is again the next position and no step kernel changes
 int session_evict_shard(vlo_session *s, int64_t t0, int64_t t1, void *stream) {
     if (!s) return fail(VLO_E_INVALID, "bad session_evict arguments");
+    if (int prc = pending_refusal(s, "session_evict")) return prc;
     vlo_engine *e = s->e;
     if (e->cfg.kv_dtype != VLO_KV_BF16)
         return fail(VLO_E_UNSUPPORTED, "session_evict: an fp8 KV pool is not re-rotated (every eviction would re-round the surviving keys to e4m3)");
@@ -1929,8 +2036,11 @@ int vlo_bench_gemv(int N, int K, int n_rows, int epi, int iters, int nbuf, doubl
 
 int vlo_debug_read(vlo_session *s, int which, void *dst_dev, int64_t bytes, void *stream) {
     if (!s || !dst_dev || bytes <= 0) return fail(VLO_E_INVALID, "bad debug_read arguments");
+    if (int prc = pending_refusal(s, "debug_read")) return prc;
     const StepWs &w = s->ws;
-    const void *src = which == 0 ? (void *)w.q : which == 1 ? (void *)w.attn : which == 2 ? (void *)w.h : which == 3 ? (void *)w.act : (void *)w.x;
+    if (which == 5 && bytes > (int64_t)16 * s->e->cfg.vocab_size * 2) return fail(VLO_E_INVALID, "debug_read: the logits buffer holds 16 rows");
+    const void *src = which == 0 ? (void *)w.q : which == 1 ? (void *)w.attn : which == 2 ? (void *)w.h : which == 3 ? (void *)w.act
+                    : which == 5 ? (void *)s->logits : (void *)w.x;
     HIP_TRY(hipMemcpyAsync(dst_dev, src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return VLO_OK;
 }

@@ -41,6 +41,14 @@ hipError_t add_rmsnorm_launch(unsigned short *h, const float *partial, int kspli
                               const unsigned short *w, unsigned short *x, int H, int ldx, float eps, int n,
                               hipStream_t st);
 
+// the same for `count` <= VLO_ROWIDX_MAX SELECTED rows (the row indices travel in the kernel arguments): x16[k] = RMSNorm(h[rows.v[k]]) * w,
+// row-major [count][H], each row bit-equal to what add_rmsnorm_launch writes for it (the pending partial sums are folded into those rows of h
+// first); the other rows of h (n_rows in all: the bound the indices are checked against) are left as they are
+#define VLO_ROWIDX_MAX 16
+struct RowIdx { int v[VLO_ROWIDX_MAX]; };
+hipError_t add_rmsnorm_gather_launch(unsigned short *h, const float *partial, int ksplit, int partial_ld, const unsigned short *w,
+                                     unsigned short *x16, int H, float eps, const RowIdx &rows, int count, int n_rows, hipStream_t st);
+
 // copy `rows` embedding rows into the residual stream h and write their sums of squares to sq_out[0..rows)
 
 // chunk attention (n <= 16 queries at positions pos0..pos0+n-1 against keys [0, pos0+n); the block path passes n <= 64
@@ -111,10 +119,25 @@ hipError_t greedy_sample_rows_launch(const unsigned short *logits, int rows, int
 hipError_t stream_sample_rows_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,
                                      float *p_interval_out, float *scratch, hipStream_t st);
 
+// stream_sample_rows_launch for the unit-end rows of a lookahead pass (rows <= VLO_ROWIDX_MAX) with the first-speaker reduction folded into
+// the finishing launch: *n_accept_out (device int) = (smallest r with tok[r] != interval_id) + 1, or rows when every row stays silent
+hipError_t stream_sample_steps_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,
+                                      float *p_interval_out, int *n_accept_out, float *scratch, hipStream_t st);
+
 #define VLO_STEP_IDS_MAX 32
 struct StepIds { int64_t v[VLO_STEP_IDS_MAX]; };      // token ids handed to step_input_kernel by value (kernel arguments)
 hipError_t step_input_launch(const unsigned short *table, const StepIds &ids, int k, const unsigned short *frame_rows, int rows, int H,
                              int64_t vocab, unsigned short *out, hipStream_t st);
+// the multi-unit form: unit u has ids v[id0[u] .. id0[u + 1]) (at most VLO_STEP_IDS_MAX for unit 0, VLO_STEPS_IDS_LATER for each later one) and
+// occupies output rows [row0[u], row0[u + 1]) = its id embeddings followed by frame rows [u * rows_per_unit, (u + 1) * rows_per_unit)
+#define VLO_STEPS_UNITS_MAX 16
+#define VLO_STEPS_IDS_LATER 4
+struct StepsIds {
+    int64_t v[VLO_STEP_IDS_MAX + (VLO_STEPS_UNITS_MAX - 1) * VLO_STEPS_IDS_LATER];
+    int id0[VLO_STEPS_UNITS_MAX + 1], row0[VLO_STEPS_UNITS_MAX + 1];
+};
+hipError_t steps_input_launch(const unsigned short *table, const StepsIds &ids, int units, const unsigned short *frame_rows, int rows_per_unit,
+                              int H, int64_t vocab, unsigned short *out, hipStream_t st);
 hipError_t copy_rows_launch(const unsigned short *src, unsigned short *dst, int rows, int H, hipStream_t st);
 hipError_t read_kv_launch(const KvPool &kv, int layer, int which, int kv_head, int64_t t0, int64_t t1, unsigned short *dst,
                           hipStream_t st);

@@ -26,14 +26,37 @@ __global__ __launch_bounds__(RMS_THREADS) void add_rmsnorm_kernel(bf16_t *__rest
                                                                   int ksplit, int partial_ld, const bf16_t *__restrict__ w,
                                                                   bf16_t *__restrict__ x, int H, int ldx, float eps) {
 #define VLO_RMS_ROW blockIdx.x
+#define VLO_RMS_XROW blockIdx.x
 #include "rmsnorm_body.inc"
 #undef VLO_RMS_ROW
+#undef VLO_RMS_XROW
+}
+
+// the same for `count` SELECTED rows (stream lookahead: the last row of each unit of a pass): block k normalises row rows.v[k] of h and writes
+// row k of the row-major x16.  The same body, so a selected row equals what add_rmsnorm_kernel writes for it bit for bit; the other rows of h
+// are neither normalised nor given their pending partial sums.
+__global__ __launch_bounds__(RMS_THREADS) void add_rmsnorm_gather_kernel(bf16_t *__restrict__ h, const float *__restrict__ partial,
+                                                                         int ksplit, int partial_ld, const bf16_t *__restrict__ w,
+                                                                         bf16_t *__restrict__ x, int H, int ldx, float eps, RowIdx rows) {
+#define VLO_RMS_ROW rows.v[blockIdx.x]
+#define VLO_RMS_XROW blockIdx.x
+#include "rmsnorm_body.inc"
+#undef VLO_RMS_ROW
+#undef VLO_RMS_XROW
 }
 
 hipError_t add_rmsnorm_launch(unsigned short *h, const float *partial, int ksplit, int partial_ld, const unsigned short *w,
                               unsigned short *x, int H, int ldx, float eps, int n, hipStream_t st) {
     if (H > 8 * RMS_THREADS * RMS_MAXCH || (H & 7)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(add_rmsnorm_kernel, dim3(n), dim3(RMS_THREADS), 0, st, h, partial, ksplit, partial_ld, w, x, H, ldx, eps);
+    return hipGetLastError();
+}
+hipError_t add_rmsnorm_gather_launch(unsigned short *h, const float *partial, int ksplit, int partial_ld, const unsigned short *w,
+                                     unsigned short *x16, int H, float eps, const RowIdx &rows, int count, int n_rows, hipStream_t st) {
+    if (H > 8 * RMS_THREADS * RMS_MAXCH || (H & 7) || count < 1 || count > VLO_ROWIDX_MAX) return hipErrorInvalidValue;
+    for (int k = 0; k < count; ++k)
+        if (rows.v[k] < 0 || rows.v[k] >= n_rows) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(add_rmsnorm_gather_kernel, dim3(count), dim3(RMS_THREADS), 0, st, h, partial, ksplit, partial_ld, w, x16, H, H, eps, rows);
     return hipGetLastError();
 }
 
@@ -561,6 +584,38 @@ hipError_t step_input_launch(const unsigned short *table, const StepIds &ids, in
     return hipGetLastError();
 }
 
+// the step inputs of SEVERAL consecutive frame steps in one launch (stream lookahead): unit u = the embeddings of its ids, then frame rows
+// [u * rows_per_unit, (u + 1) * rows_per_unit).  Block r finds its unit in the row table (at most VLO_STEPS_UNITS_MAX entries, kernel arguments)
+// and copies its row exactly as step_input_kernel does.
+__global__ void steps_input_kernel(const bf16_t *__restrict__ table, StepsIds ids, int units, const bf16_t *__restrict__ frame_rows,
+                                   int rows_per_unit, int H, int64_t vocab, bf16_t *__restrict__ out) {
+    const int r = blockIdx.x;
+    int u = 0;
+    while (u + 1 < units && r >= ids.row0[u + 1]) ++u;
+    const int j = r - ids.row0[u], k = ids.id0[u + 1] - ids.id0[u];
+    const uint4 *src;
+    if (j < k) {
+        int64_t id = ids.v[ids.id0[u] + j];
+        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        src = reinterpret_cast<const uint4 *>(table + (size_t)id * H);
+    } else {
+        src = reinterpret_cast<const uint4 *>(frame_rows + ((size_t)u * rows_per_unit + (j - k)) * H);
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)r * H);
+    for (int i = threadIdx.x; i < H / 8; i += blockDim.x) dst[i] = src[i];
+}
+hipError_t steps_input_launch(const unsigned short *table, const StepsIds &ids, int units, const unsigned short *frame_rows, int rows_per_unit,
+                              int H, int64_t vocab, unsigned short *out, hipStream_t st) {
+    if (units < 1 || units > VLO_STEPS_UNITS_MAX || rows_per_unit < 0 || (H & 7) || ids.row0[0] != 0 || ids.id0[0] != 0) return hipErrorInvalidValue;
+    for (int u = 0; u < units; ++u) {
+        const int k = ids.id0[u + 1] - ids.id0[u];
+        if (k < 0 || k > (u ? VLO_STEPS_IDS_LATER : VLO_STEP_IDS_MAX) || ids.row0[u + 1] != ids.row0[u] + k + rows_per_unit) return hipErrorInvalidValue;
+    }
+    if (ids.row0[units] < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(steps_input_kernel, dim3(ids.row0[units]), dim3(256), 0, st, table, ids, units, frame_rows, rows_per_unit, H, vocab, out);
+    return hipGetLastError();
+}
+
 __global__ void copy_rows_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
@@ -741,6 +796,41 @@ hipError_t stream_sample_launch(const unsigned short *logits, int V, float thres
     hipLaunchKernelGGL(sample_stats_kernel, dim3(SAMPLE_BLOCKS), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
     hipLaunchKernelGGL(stream_scan_kernel, dim3(SAMPLE_BLOCKS), dim3(SAMPLE_THREADS), 0, st, logits, V, threshold, interval_id, scratch);
     hipLaunchKernelGGL(stream_final_kernel, dim3(1), dim3(64), 0, st, scratch, SAMPLE_BLOCKS, tok_out, p_interval_out);
+    return hipGetLastError();
+}
+// the finishing launch of the sampler over the `rows` unit-end rows of a lookahead pass: wave r of the ONE block finishes row r as
+// stream_final_body does (one partial per lane, the same wave_argbest), then thread 0 writes the first-speaker count
+// *n_accept = (smallest r with tok[r] != interval_id) + 1, or rows when every row stays silent.
+__global__ __launch_bounds__(64 * VLO_ROWIDX_MAX) void stream_final_steps_kernel(const float *__restrict__ scr_rows, int NB, int rows, int interval_id,
+                                                                               int64_t *tok_out, float *p_interval_out, int *n_accept) {
+    __shared__ int toks[VLO_ROWIDX_MAX];
+    const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (r < rows) {
+        const float *scr = scr_rows + (size_t)r * VLO_SAMPLE_SCRATCH_FLOATS;
+        ArgBest b = {-INFINITY, 0x7fffffff};
+        for (int k = lane; k < NB; k += 64) b = better(b, (ArgBest){scr[4 * NB + k], reinterpret_cast<const int *>(scr)[5 * NB + k]});
+        b = wave_argbest(b);
+        if (lane == 0) {
+            toks[r] = b.i;
+            tok_out[r] = b.i;
+            if (p_interval_out) p_interval_out[r] = scr[6 * NB];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int acc = rows;
+        for (int k = rows - 1; k >= 0; --k)
+            if (toks[k] != interval_id) acc = k + 1;
+        *n_accept = acc;
+    }
+}
+hipError_t stream_sample_steps_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,
+                                      float *p_interval_out, int *n_accept_out, float *scratch, hipStream_t st) {
+    if (interval_id < 0 || interval_id >= V || rows < 1 || rows > VLO_ROWIDX_MAX || !n_accept_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_stats_rows_kernel, dim3(SAMPLE_BLOCKS, rows), dim3(SAMPLE_THREADS), 0, st, logits, V, scratch);
+    hipLaunchKernelGGL(stream_scan_rows_kernel, dim3(SAMPLE_BLOCKS, rows), dim3(SAMPLE_THREADS), 0, st, logits, V, threshold, interval_id, scratch);
+    hipLaunchKernelGGL(stream_final_steps_kernel, dim3(1), dim3(64 * rows), 0, st, scratch, SAMPLE_BLOCKS, rows, interval_id, tok_out, p_interval_out,
+                       n_accept_out);
     return hipGetLastError();
 }
 hipError_t stream_sample_rows_launch(const unsigned short *logits, int rows, int V, float threshold, int interval_id, int64_t *tok_out,

@@ -1,4 +1,5 @@
-// rmsnorm_body.inc — body of add_rmsnorm_kernel (llm_ops.hip), included textually by the kernel (VLO_RMS_ROW = blockIdx.x).
+// rmsnorm_body.inc — body of add_rmsnorm_kernel and add_rmsnorm_gather_kernel (llm_ops.hip), included textually by the kernel.
+// VLO_RMS_ROW = the row of h / partial the block normalises, VLO_RMS_XROW = the row of x it writes (both blockIdx.x in add_rmsnorm_kernel).
 // Expects the kernel's parameters by name in scope.
     __shared__ float sm[16];
     const int m = VLO_RMS_ROW;
@@ -44,7 +45,8 @@
     }
     ss = block_sum(ss, sm);
     const float rs = 1.0f / sqrtf(ss / (float)H + eps);
-    bf16_t *xr = x + (size_t)m * ldx;
+    const int mx = VLO_RMS_XROW;
+    bf16_t *xr = x + (size_t)mx * ldx;
 #pragma unroll
     for (int c = 0; c < RMS_MAXCH; ++c) {
         const int ch = threadIdx.x + c * RMS_THREADS;
@@ -54,7 +56,7 @@
             bf16_t *oe = reinterpret_cast<bf16_t *>(&o);
 #pragma unroll
             for (int j = 0; j < 8; ++j) oe[j] = f2bf(bf2f(we[j]) * rbf(v[c][j] * rs));   // weight * x.to(bf16)
-            bf16_t *dst = ldx ? xr + ch * 8 : x + vlo_pack64_elem(m, ch * 8);            // ldx == 0: packed-64 (block path)
+            bf16_t *dst = ldx ? xr + ch * 8 : x + vlo_pack64_elem(mx, ch * 8);            // ldx == 0: packed-64 (block path)
             *reinterpret_cast<uint4 *>(dst) = o;
         }
     }

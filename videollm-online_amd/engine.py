@@ -138,6 +138,24 @@ class Session:
         (include/vlo.h vlo_session_evict), so the length is again the next position.  Ordered on ``stream``; bf16 KV pools only."""
         _C.check(_C.lib().vlo_session_evict(self._h, t0, t1, _stream_handle(stream)))
 
+    def stream_steps(self, embeds: torch.Tensor, unit_ends: list, threshold: float, interval_id: int, tok_out: torch.Tensor,
+                     p_out: torch.Tensor | None, accept_out: torch.Tensor, stream=None):
+        """A backlog of frame steps in one weight pass (include/vlo.h vlo_stream_steps): ``embeds`` bf16 [n, H] holds ``len(unit_ends)``
+        consecutive step inputs, unit k ending at row ``unit_ends[k]``.  ``tok_out`` int64 [>= units], ``p_out`` f32 [>= units] or None,
+        ``accept_out`` int32 [1] receive the sampler's tokens, p[interval] and the first-speaker count.  The session is then pending
+        until ``commit_steps``."""
+        units, H = len(unit_ends), self.engine.cfg.hidden_size
+        assert embeds.dtype == torch.bfloat16 and embeds.is_contiguous() and embeds.dim() == 2 and embeds.shape[1] == H
+        assert tok_out.dtype == torch.long and tok_out.numel() >= units and accept_out.dtype == torch.int32 and accept_out.numel() >= 1
+        assert p_out is None or (p_out.dtype == torch.float32 and p_out.numel() >= units)
+        ends = (C.c_int * max(units, 1))(*unit_ends)
+        _C.check(_C.lib().vlo_stream_steps(self._h, _ptr(embeds), embeds.shape[0], ends, units, threshold, interval_id, _ptr(tok_out),
+                                           _ptr(p_out) if p_out is not None else None, _ptr(accept_out), _stream_handle(stream)))
+
+    def commit_steps(self, keep: int):
+        """Keep the first ``keep`` units of the pending pass (vlo_stream_steps_commit); the rest is cropped."""
+        _C.check(_C.lib().vlo_stream_steps_commit(self._h, keep))
+
     def read_kv(self, layer, which, kv_head, t0, t1):
         out = torch.empty(t1 - t0, self.engine.head_dim, dtype=torch.bfloat16, device=self.engine.device)
         _C.check(_C.lib().vlo_session_read_kv(self._h, layer, which, kv_head, t0, t1, _ptr(out), _stream_handle()))
@@ -334,6 +352,27 @@ class Engine:
         arr = (C.c_int64 * max(k, 1))(*ids)
         _C.check(_C.lib().vlo_step_input(self._h, arr, k, _ptr(frame_rows) if rows else None, rows, _ptr(out), _stream_handle(stream)))
         return out[:k + rows]
+
+    def steps_input(self, ids_per_unit: list, frame_rows: list, out: torch.Tensor, stream=None) -> torch.Tensor:
+        """The step inputs of several consecutive frame steps in one launch (include/vlo.h vlo_steps_input): unit u =
+        ``embed(ids_per_unit[u])`` followed by ``frame_rows[u]`` (bf16 [rows, H], the same row count for every unit), written into the
+        caller's staging buffer ``out``.  Frame rows that are consecutive slices of one encode batch are read in place; others are
+        gathered with one ``torch.cat`` first.  Returns the view of ``out`` that was written."""
+        units, H = len(ids_per_unit), self.cfg.hidden_size
+        assert units == len(frame_rows) and units >= 1
+        rows = frame_rows[0].shape[0]
+        for f in frame_rows:
+            assert f.dtype == torch.bfloat16 and f.is_contiguous() and tuple(f.shape) == (rows, H)
+        base = frame_rows[0]
+        if any(f.data_ptr() != base.data_ptr() + u * rows * H * 2 for u, f in enumerate(frame_rows)):
+            base = torch.cat(frame_rows)
+        ks = [len(i) for i in ids_per_unit]
+        total = sum(ks) + units * rows
+        assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape[0] >= total and out.shape[1] == H
+        flat = [i for u in ids_per_unit for i in u]
+        _C.check(_C.lib().vlo_steps_input(self._h, (C.c_int64 * max(len(flat), 1))(*flat), (C.c_int * units)(*ks), units, _ptr(base), rows,
+                                          _ptr(out), _stream_handle(stream)))
+        return out[:total]
 
     def connector(self, feats: torch.Tensor, stream=None) -> torch.Tensor:
         feats = feats.to(device=self.device, dtype=torch.bfloat16).contiguous().view(-1, self.cfg.vision_hidden_size)

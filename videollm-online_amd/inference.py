@@ -30,6 +30,9 @@ class StreamTokens:
     query_ids: dict = field(default_factory=dict)
 
 
+LOOKAHEAD_MAX_UNITS = 16   # frames of one lookahead pass (include/vlo.h vlo_stream_steps: units <= 16)
+LOOKAHEAD_MAX_ROWS = 64    # rows of one lookahead pass (csrc VLO_BLOCK_TOKENS)
+LOOKAHEAD_IDS_MAX = 32     # ids the first unit of vlo_steps_input can carry
 KV_PAGE_TOKENS = 256       # tokens of one KV page (csrc/llm_ops.h VLO_PAGE_TOKENS): the hysteresis of KvBudget
 
 
@@ -80,7 +83,7 @@ class LiveInfer:
     def __init__(self, model: LiveModel, tokens: StreamTokens | None = None, tokenizer=None, frame_fps: float = 2,
                  system_prompt: str = "", prefetch: bool = True, prefetch_frames: int = 2, schedule=None,
                  max_new_tokens: int = 100, record: int = 65536, encode_stream=None, kv_budget: int | None = None,
-                 kv_sink: int | None = None):
+                 kv_sink: int | None = None, lookahead: int = 1):
         self.model = model
         self.engine = model.engine
         self.tokenizer = tokenizer
@@ -128,10 +131,25 @@ class LiveInfer:
         # step input staging (demo/inference.py:61-68): text rows + this frame's rows, written by ONE launch (vlo_step_input);
         # sized for the longest text prefix a frame step can carry; longer ones (a long system prompt) grow it
         self._stage = torch.empty(64 + self.frame_num_tokens, self.hidden_size, dtype=torch.bfloat16, device=dev)
+        # stream lookahead: up to ``lookahead`` queued frames go through the Llama as ONE weight pass (include/vlo.h vlo_stream_steps): after a
+        # silent frame the next step's input is [interval_id] + frame rows, so a backlog is a single causal pass; what follows the first frame
+        # that speaks is discarded and its frames go back to the queue.  1 (the default): every frame is stepped alone, no new call is made
+        self.lookahead = int(lookahead)
+        if self.lookahead < 1:
+            raise ValueError(f"lookahead must be >= 1, got {lookahead}")
+        if self.lookahead > 1:
+            if not hasattr(self.engine, "steps_input"):
+                raise ValueError("lookahead > 1 needs a single-GPU engine (vlo_stream_steps is not available on tensor-parallel groups)")
+            self._toks_dev = torch.zeros(LOOKAHEAD_MAX_UNITS, dtype=torch.long, device=dev)
+            self._ps_dev = torch.zeros(LOOKAHEAD_MAX_UNITS, dtype=torch.float32, device=dev)
+            self._accept_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._toks_host = torch.zeros(LOOKAHEAD_MAX_UNITS, dtype=torch.long).pin_memory()
+            self._accept_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         # event log for tests / the bench: bounded (a long-running session must not grow host memory), cleared by reset()
         self._record = max(0, int(record))
         # bounded context (None = the reference's ever-growing cache, no eviction call is ever made): see KvBudget.  The KV pool must
-        # hold the budget plus the step or response that crosses it: the eviction runs AFTER that step
+        # hold the budget plus the step or response that crosses it: the eviction runs AFTER that step.  With lookahead > 1 that step is one pass
+        # of up to LOOKAHEAD_MAX_ROWS (64) rows: the pool must hold the budget plus 64 tokens
         self._kv_budget = None
         if kv_budget is not None:
             longest_step = 1 + len(self._added_stream_prompt_ids) + self.frame_num_tokens   # [eos] + stream prompt + the frame
@@ -167,6 +185,8 @@ class LiveInfer:
         self.trace = collections.deque(maxlen=self._record or 1)       # trace.FrameEvent / trace.ResponseEvent, newest last
         self.step_log = collections.deque(maxlen=self._record or 1)    # (cache length before, new tokens) of the Llama steps
         self.steps_total = 0               # Llama steps executed since reset() (step_log keeps the newest `record` of them)
+        self.lookahead_passes = 0          # multi-frame passes run (lookahead > 1)
+        self.lookahead_discarded = 0       # units of those passes thrown away behind a frame that spoke (their frames were requeued)
         if self._kv_budget is not None:
             self._kv_budget.clear()
 
@@ -318,56 +338,151 @@ class LiveInfer:
         return query, response
 
     def _call_for_streaming(self):                                     # :54-82
-        eng = self.engine
         while self.frame_embeds_queue:
             # 1. if query is before next frame, response
             if self.query_queue and self.frame_embeds_queue[0][0] > self.query_queue[0][0]:
                 video_time, query = self.query_queue.popleft()
                 return video_time, query
-            video_time, (frame_embeds, ready) = self.frame_embeds_queue.popleft()
-            if not self.past_key_values:
-                self.last_ids = list(self._start_ids)
-            elif self.last_ids == [self.eos_token_id]:
-                self.last_ids = self.last_ids + self._added_stream_prompt_ids
-            if self.past_key_values is None:
-                self.past_key_values = self.model.new_cache()
-            self._main.wait_event(ready)
-            if len(self.last_ids) + self.frame_num_tokens > self._stage.shape[0]:
-                self._stage = torch.empty(len(self.last_ids) + self.frame_num_tokens, self.hidden_size, dtype=torch.bfloat16,
-                                          device=self.model.device)
-            with stage("step"):
-                inputs_embeds = eng.step_input(self.last_ids, frame_embeds, self._stage)      # :61-68 without torch.tensor / torch.cat
-                self._log_step(len(self.past_key_values), inputs_embeds.shape[0])
-                eng.llm_step(self.past_key_values, inputs_embeds, want_last=False)
-            self._frames_done += 1
-            nxt = self.last_frame_idx + 1
-            if self.prefetch and not self.frame_embeds_queue and nxt not in self._encoded:
-                # the next frame(s) are encoded on the encode stream while this Llama step runs; the encode is
-                # enqueued here, AFTER the step's own launches, so the host never delays the step
-                self._encode_async(nxt, nxt + self.prefetch_frames)
-            # 2. if the same time, response after frame at that time
-            if self.query_queue and video_time >= self.query_queue[0][0]:
-                self._enforce_kv_budget(video_time)
-                video_time, query = self.query_queue.popleft()
-                return video_time, query
-            # 3. if the next is frame but next is not interval, then response
-            with stage("sample"):
-                eng.stream_sample(self.past_key_values, self.frame_token_interval_threshold, self.frame_token_interval_id,
-                                  tok_out=self._tok_dev, p_out=self._p_dev)
-                self._tok_host.copy_(self._tok_dev, non_blocking=True)
-                self._main.synchronize()
-            tok = sampled = int(self._tok_host[0])
-            forced = self.schedule(self._frames_done - 1) if self.schedule is not None else None
-            if forced is not None:
-                tok = self._added_stream_generation_ids[0] if forced[0] else self.frame_token_interval_id
-            self.last_ids = [tok]
-            if self._record:
-                # trace.FrameEvent: the sampler's own choice differs from the token used only under a schedule
-                self.trace.append(frame_event(video_time, tok, len(self.past_key_values), sampled))
-            self._enforce_kv_budget(video_time)
-            if tok != self.frame_token_interval_id:
-                return video_time, None
+            out = self._lookahead_pass() if self._lookahead_fits() else self._frame_step()
+            if out is not None:
+                return out
         return None, None
+
+    def _next_step_ids(self):
+        """The text ids the next frame step carries in front of its frame rows (:61-65)."""
+        if not self.past_key_values:
+            return list(self._start_ids)
+        if self.last_ids == [self.eos_token_id]:
+            return self.last_ids + self._added_stream_prompt_ids
+        return self.last_ids
+
+    def _frame_step(self):
+        """One queued frame stepped alone (the reference's loop body).  Returns (video_time, query | None) when a response is due, else None."""
+        eng = self.engine
+        video_time, (frame_embeds, ready) = self.frame_embeds_queue.popleft()
+        self.last_ids = self._next_step_ids()
+        if self.past_key_values is None:
+            self.past_key_values = self.model.new_cache()
+        self._main.wait_event(ready)
+        if len(self.last_ids) + self.frame_num_tokens > self._stage.shape[0]:
+            self._stage = torch.empty(len(self.last_ids) + self.frame_num_tokens, self.hidden_size, dtype=torch.bfloat16,
+                                      device=self.model.device)
+        with stage("step"):
+            inputs_embeds = eng.step_input(self.last_ids, frame_embeds, self._stage)      # :61-68 without torch.tensor / torch.cat
+            self._log_step(len(self.past_key_values), inputs_embeds.shape[0])
+            eng.llm_step(self.past_key_values, inputs_embeds, want_last=False)
+        self._frames_done += 1
+        self._prefetch_next()
+        # 2. if the same time, response after frame at that time
+        if self.query_queue and video_time >= self.query_queue[0][0]:
+            self._enforce_kv_budget(video_time)
+            video_time, query = self.query_queue.popleft()
+            return video_time, query
+        # 3. if the next is frame but next is not interval, then response
+        with stage("sample"):
+            eng.stream_sample(self.past_key_values, self.frame_token_interval_threshold, self.frame_token_interval_id,
+                              tok_out=self._tok_dev, p_out=self._p_dev)
+            self._tok_host.copy_(self._tok_dev, non_blocking=True)
+            self._main.synchronize()
+        tok = sampled = int(self._tok_host[0])
+        forced = self.schedule(self._frames_done - 1) if self.schedule is not None else None
+        if forced is not None:
+            tok = self._added_stream_generation_ids[0] if forced[0] else self.frame_token_interval_id
+        self.last_ids = [tok]
+        if self._record:
+            # trace.FrameEvent: the sampler's own choice differs from the token used only under a schedule
+            self.trace.append(frame_event(video_time, tok, len(self.past_key_values), sampled))
+        self._enforce_kv_budget(video_time)
+        if tok != self.frame_token_interval_id:
+            return video_time, None
+        return None
+
+    def _prefetch_next(self):
+        nxt = self.last_frame_idx + 1
+        if self.prefetch and not self.frame_embeds_queue and nxt not in self._encoded:
+            # the next frame(s) are encoded on the encode stream while this Llama step runs; the encode is
+            # enqueued here, AFTER the step's own launches, so the host never delays the step
+            self._encode_async(nxt, nxt + self.prefetch_frames)
+
+    def _lookahead_fits(self):
+        """Does the next frame step go through a lookahead pass: lookahead is on and its text prefix fits the pass's first unit."""
+        if self.lookahead <= 1:
+            return False
+        k = len(self._next_step_ids())
+        return k <= LOOKAHEAD_IDS_MAX and k + self.frame_num_tokens <= LOOKAHEAD_MAX_ROWS
+
+    def _lookahead_pass(self):
+        """Up to ``lookahead`` queued frames as one weight pass (include/vlo.h vlo_stream_steps).  The run of frames ends where the reference's
+        queue rules would interrupt the per-frame loop: before a frame that a due query precedes (rule 1), after a frame at or behind a due
+        query (rule 2: the query is answered after it), after the first frame a schedule makes speak.  The sampler decides every unit; the
+        commit keeps the units up to the first that speaks, the frames behind it go back to the front of the queue (nothing is encoded
+        again).  Returns what _frame_step returns."""
+        eng, T, iid = self.engine, self.frame_num_tokens, self.frame_token_interval_id
+        ids0 = self._next_step_ids()
+        if self.past_key_values is None:
+            self.past_key_values = self.model.new_cache()
+        units, forced, rows, answer_after = [], [], 0, False
+        while self.frame_embeds_queue and len(units) < min(self.lookahead, LOOKAHEAD_MAX_UNITS):
+            t = self.frame_embeds_queue[0][0]
+            k = len(ids0) if not units else 1
+            if units and (rows + k + T > LOOKAHEAD_MAX_ROWS or (self.query_queue and t > self.query_queue[0][0])):
+                break
+            units.append(self.frame_embeds_queue.popleft())
+            rows += k + T
+            forced.append(self.schedule(self._frames_done + len(units) - 1) if self.schedule is not None else None)
+            if self.query_queue and t >= self.query_queue[0][0]:
+                answer_after = True
+                break
+            if forced[-1] is not None and forced[-1][0]:
+                break
+        ids = [ids0] + [[iid]] * (len(units) - 1)
+        ends, r = [], 0
+        for u in ids:
+            r += len(u) + T
+            ends.append(r - 1)
+        for _, (_, ready) in units:
+            self._main.wait_event(ready)
+        L0 = len(self.past_key_values)
+        n = len(units)
+        with stage("step"):
+            x = eng.steps_input(ids, [f for _, (f, _) in units], self._stage)
+            self.past_key_values.stream_steps(x, ends, self.frame_token_interval_threshold, iid, self._toks_dev, self._ps_dev, self._accept_dev)
+        self._prefetch_next()
+        with stage("sample"):
+            self._toks_host.copy_(self._toks_dev, non_blocking=True)
+            self._accept_host.copy_(self._accept_dev, non_blocking=True)
+            self._main.synchronize()
+        sampled = self._toks_host[:n].tolist()
+        toks = list(sampled)
+        for j, f in enumerate(forced):
+            if f is not None:
+                toks[j] = self._added_stream_generation_ids[0] if f[0] else iid
+        decided = n - 1 if answer_after else n             # rule 2: the last unit's token is not looked at, the query is answered after it
+        if self.schedule is None and not answer_after:
+            keep = int(self._accept_host[0])               # the first-speaker count of the device, = the restatement below
+        else:
+            keep = next((j + 1 for j in range(decided) if toks[j] != iid), n)
+        self.past_key_values.commit_steps(keep)
+        self.lookahead_passes += 1
+        self.lookahead_discarded += n - keep
+        self.frame_embeds_queue.extendleft(reversed(units[keep:]))
+        video_time = None
+        for j in range(keep):
+            video_time = units[j][0]
+            self._log_step(L0 + (ends[j - 1] + 1 if j else 0), len(ids[j]) + T)
+            self._frames_done += 1
+            if answer_after and j == n - 1:
+                break
+            self.last_ids = [toks[j]]
+            if self._record:
+                self.trace.append(frame_event(video_time, toks[j], L0 + ends[j] + 1, sampled[j]))
+        self._enforce_kv_budget(video_time)
+        if answer_after and keep == n:
+            video_time, query = self.query_queue.popleft()
+            return video_time, query
+        if toks[keep - 1] != iid:
+            return video_time, None
+        return None
 
     def __call__(self):                                                # :117-123
         if not self.frame_embeds_queue:
