@@ -306,6 +306,19 @@ int vlo_session_crop(vlo_session *s, int64_t n_tokens);
  *      (nearest even).  V is moved bit for bit.  After the call `len` is again the next RoPE position, so positions never outgrow the
  *      pool's tables however long the stream runs; a key that survives n evictions has been rounded n + 1 times. */
 int vlo_session_evict(vlo_session *s, int64_t t0, int64_t t1, void *stream);
+/* Several ranges in ONE pass: forget [a_j, b_j), j < n, given in the cache coordinates BEFORE the call as ranges_host[j] = {a_j, b_j} (host
+ *      memory, read before the call returns).  0 <= a_j <= b_j <= len, ascending and non-overlapping (b_j <= a_{j+1}), else VLO_E_INVALID;
+ *      empty ranges are dropped and touching ones merged, and what is left may be at most VLO_EVICT_MAX_RANGES ranges (VLO_E_INVALID), or
+ *      nothing (a no-op).  The whole call is validated before anything is launched or changed.  Survivors keep their order: a survivor at
+ *      position p moves to p - D(p), D(p) = the number of evicted positions below p, and its key is re-rotated by -D(p) positions with the rule
+ *      above (d = D(p): the host computes one (c, s) row per survivor run, they travel through a small device table), rounded ONCE to bf16:
+ *      a key that survives a call is rounded once by it, however many ranges lie below it — R single vlo_session_evict calls round it up to
+ *      R times and move the tail R times.  V is moved bit for bit; positions below a_0 are untouched; a last range that ends at len is a crop
+ *      (nothing is moved for it).  len becomes len - D(len); pages, logits, stream order, fp8 pools (VLO_E_UNSUPPORTED) and a pending
+ *      vlo_stream_steps pass (VLO_E_STATE): as vlo_session_evict.  n = 1 leaves the cache bit-identical to vlo_session_evict(a_0, b_0).
+ *      Calls may follow each other on a stream without a host synchronise in between. */
+#define VLO_EVICT_MAX_RANGES 64
+int vlo_session_evict_ranges(vlo_session *s, const int64_t *ranges_host /* [n][2] */, int n, void *stream);
 
 /* ---- tensor parallelism (north_star; new capability — the reference has none) -------------------
  * Engines created with vlo_config.tp_size = T > 1 / tp_rank = r hold rank r's shard (load_weight still takes the FULL
@@ -333,6 +346,7 @@ void vlo_tp_session_destroy(vlo_tp_session *t);
 int  vlo_tp_session_fork(vlo_tp_session *src, int64_t n_tokens, vlo_tp_session **out, void *stream);
 int  vlo_tp_session_crop(vlo_tp_session *t, int64_t n_tokens);
 int  vlo_tp_session_evict(vlo_tp_session *t, int64_t t0, int64_t t1, void *stream);   /* vlo_session_evict on every local shard alike */
+int  vlo_tp_session_evict_ranges(vlo_tp_session *t, const int64_t *ranges_host, int n, void *stream);   /* vlo_session_evict_ranges likewise */
 int  vlo_tp_llm_step(vlo_tp_session *t, const void *embeds_dev, int n, void *last_logits_dev, void *all_logits_dev, void *stream);
 int  vlo_tp_stream_sample(vlo_tp_session *t, float threshold, int interval_id, int64_t *tok_dev, float *p_interval_dev, void *stream);
 int  vlo_tp_greedy_generate(vlo_tp_session *t, const void *embeds_dev, int m, int eos_token_id, int64_t *out_ids_dev, int max_new,

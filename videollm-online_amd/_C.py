@@ -43,6 +43,7 @@ EXPORTS = [
     "vlo_tp_session_fork", "vlo_tp_session_crop", "vlo_session_evict", "vlo_tp_session_evict",
     "vlo_batch_create", "vlo_batch_destroy", "vlo_batch_step", "vlo_batch_stream_sample", "vlo_batch_greedy_generate",
     "vlo_test_gemv_mxfp4", "vlo_stream_steps", "vlo_stream_steps_commit", "vlo_steps_input",
+    "vlo_session_evict_ranges", "vlo_tp_session_evict_ranges",
 ]
 
 
@@ -133,6 +134,8 @@ def bind(L):
     L.vlo_tp_session_crop.argtypes = [vp, i64]
     L.vlo_session_evict.argtypes = [vp, i64, i64, vp]
     L.vlo_tp_session_evict.argtypes = [vp, i64, i64, vp]
+    L.vlo_session_evict_ranges.argtypes = [vp, C.POINTER(i64), i32, vp]
+    L.vlo_tp_session_evict_ranges.argtypes = [vp, C.POINTER(i64), i32, vp]
     L.vlo_batch_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.vlo_batch_destroy.argtypes = [vp]
     L.vlo_batch_destroy.restype = None

@@ -50,6 +50,7 @@ struct PrefillWs {
     void *xq = nullptr;
 };
 
+#define VLO_EVICT_SLOTS 4            // ring of vlo_session_evict_ranges table buffers (see vlo_engine)
 struct vlo_engine {
     vlo_config cfg{};
     int device = 0;
@@ -80,6 +81,16 @@ struct vlo_engine {
     int64_t page_elems = 0, layer_stride = 0;
     std::vector<int> free_pages;
     std::mutex pool_mu;
+
+    // vlo_session_evict_ranges: the segment / (c, s) table of a call changes with every call and is too large for kernel arguments.  As a
+    // batch's step tables (vlo_batch): slot k is written on the host (pinned evict_stage[k]), copied to evict_dev[k] on the call's stream and read
+    // by its kernel; evict_ev[k], recorded behind the kernel, must have completed before the host rewrites the slot.  Allocated on first use,
+    // guarded by evict_mu (sessions of one engine may evict from threads and streams of their own)
+    KvEvictTable *evict_stage = nullptr, *evict_dev = nullptr;
+    hipEvent_t evict_ev[VLO_EVICT_SLOTS] = {};
+    bool evict_used[VLO_EVICT_SLOTS] = {};
+    int evict_slot = 0;
+    std::mutex evict_mu;
 
 
     VitState *vit = nullptr;
@@ -200,4 +211,9 @@ int connector_run(vlo_engine *e, int slot, const void *feats_dev, int rows, void
 int session_fork_shard(vlo_session *src, int64_t n_tokens, vlo_session **out, void *stream);   // one KV shard (engine.hip)
 int session_crop_shard(vlo_session *s, int64_t n_tokens);
 int session_evict_shard(vlo_session *s, int64_t t0, int64_t t1, void *stream);
+// vlo_session_evict_ranges in two halves, so that a tensor-parallel call is validated as a whole before any shard moves: evict_ranges_normalize
+// checks `ranges_host` ([n][2], 0 <= a <= b <= len, ascending, non-overlapping) and returns the non-empty ranges with touching ones merged
+// (at most VLO_EVICT_MAX_RANGES, else VLO_E_INVALID); session_evict_ranges_shard evicts such a list from ONE KV shard
+int evict_ranges_normalize(const int64_t *ranges_host, int n, int64_t len, std::vector<std::pair<int64_t, int64_t>> *out);
+int session_evict_ranges_shard(vlo_session *s, const std::vector<std::pair<int64_t, int64_t>> &ranges, void *stream);
 int vlo_fail(int code, const std::string &msg);   // sets the thread-local error string, returns code

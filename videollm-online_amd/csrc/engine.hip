@@ -150,6 +150,9 @@ void vlo_engine_destroy(vlo_engine *e) {
     for (const PrefillWs &w : e->prefill_free)
         for (void *p : {(void *)w.ph, (void *)w.px, (void *)w.pqkv, (void *)w.pq, (void *)w.pact, w.wexp, (void *)w.partial, w.xq}) if (p) hipFree(p);
     for (auto &pr : e->prof_events) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    if (e->evict_stage) hipHostFree(e->evict_stage);
+    if (e->evict_dev) hipFree(e->evict_dev);
+    for (hipEvent_t ev : e->evict_ev) if (ev) hipEventDestroy(ev);
     vit_destroy(e);
     ingest_destroy(e);
     delete e;
@@ -1810,6 +1813,114 @@ int session_evict_shard(vlo_session *s, int64_t t0, int64_t t1, void *stream) {
 int vlo_session_evict(vlo_session *s, int64_t t0, int64_t t1, void *stream) {
     if (s && s->e->tp_size > 1) return fail(VLO_E_STATE, "a tensor-parallel shard is evicted through vlo_tp_session_evict");
     return session_evict_shard(s, t0, t1, stream);
+}
+
+// ---- eviction of several ranges in one pass (vlo.h vlo_session_evict_ranges) --------------------------------------------------------------
+int evict_ranges_normalize(const int64_t *ranges_host, int n, int64_t len, std::vector<std::pair<int64_t, int64_t>> *out) {
+    out->clear();
+    if (n < 0 || (n > 0 && !ranges_host)) return fail(VLO_E_INVALID, "bad session_evict_ranges arguments");
+    int64_t prev = 0;
+    for (int j = 0; j < n; ++j) {
+        const int64_t a = ranges_host[2 * j], b = ranges_host[2 * j + 1];
+        if (a < prev || b < a || b > len)
+            return fail(VLO_E_INVALID, "bad session_evict_ranges arguments: range " + std::to_string(j) + " = [" + std::to_string(a) + ", " + std::to_string(b) +
+                                           "): need 0 <= a <= b <= len, ascending, non-overlapping");
+        prev = b;
+        if (a == b) continue;
+        if (!out->empty() && out->back().second == a) out->back().second = b;
+        else out->emplace_back(a, b);
+    }
+    if (out->size() > VLO_EVICT_MAX_RANGES)
+        return fail(VLO_E_INVALID, "session_evict_ranges: " + std::to_string(out->size()) + " ranges after merging (at most " + std::to_string(VLO_EVICT_MAX_RANGES) + " per call)");
+    return VLO_OK;
+}
+
+// the engine's table ring, allocated at the first call that moves something
+static int evict_ring(vlo_engine *e) {
+    if (e->evict_dev) return VLO_OK;
+    if (!e->evict_stage && hipHostMalloc((void **)&e->evict_stage, sizeof(KvEvictTable) * VLO_EVICT_SLOTS, hipHostMallocDefault) != hipSuccess) {
+        e->evict_stage = nullptr;
+        return fail(VLO_E_HIP, "hipHostMalloc failed");
+    }
+    for (hipEvent_t &ev : e->evict_ev)
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    void *p = nullptr;
+    if (int rc = dev_alloc(&p, sizeof(KvEvictTable) * VLO_EVICT_SLOTS)) return rc;
+    e->evict_dev = (KvEvictTable *)p;
+    return VLO_OK;
+}
+
+// `ranges`: what evict_ranges_normalize returned for this shard's length.  The survivor run behind range j is segment j; a last range that
+// ends at len leaves no run behind it (a crop)
+int session_evict_ranges_shard(vlo_session *s, const std::vector<std::pair<int64_t, int64_t>> &ranges, void *stream) {
+    if (!s) return fail(VLO_E_INVALID, "bad session_evict_ranges arguments");
+    if (int prc = pending_refusal(s, "session_evict_ranges")) return prc;
+    vlo_engine *e = s->e;
+    if (e->cfg.kv_dtype != VLO_KV_BF16)
+        return fail(VLO_E_UNSUPPORTED, "session_evict_ranges: an fp8 KV pool is not re-rotated (every eviction would re-round the surviving keys to e4m3)");
+    if (ranges.empty()) return VLO_OK;
+    if (ranges.size() > VLO_EVICT_MAX_RANGES || ranges.front().first < 0 || ranges.back().second > s->len)
+        return fail(VLO_E_INVALID, "bad session_evict_ranges arguments");
+    HIP_TRY(hipSetDevice(e->device));
+    const int n_seg = (int)ranges.size() - (ranges.back().second == s->len ? 1 : 0);
+    int64_t D = 0;
+    for (const auto &r : ranges) D += r.second - r.first;
+    const int64_t nl = s->len - D;
+    if (n_seg > 0) {
+        const int half = e->head_dim / 2;
+        if (half > 64 || (e->head_dim != 64 && e->head_dim != 128) || (int)e->inv_freq_h.size() != half)
+            return fail(VLO_E_UNSUPPORTED, "session_evict_ranges: head_dim must be 64 or 128");
+        std::lock_guard<std::mutex> g(e->evict_mu);
+        if (int rc = evict_ring(e)) return rc;
+        const int k = e->evict_slot;
+        if (e->evict_used[k]) HIP_TRY(hipEventSynchronize(e->evict_ev[k]));   // the call that last used slot k has read it
+        KvEvictTable &T = e->evict_stage[k];
+        int64_t Dj = 0;
+        for (int j = 0; j < n_seg; ++j) {
+            Dj += ranges[j].second - ranges[j].first;
+            T.w[j] = ranges[j].second - Dj;
+            T.D[j] = Dj;
+            for (int i = 0; i < half; ++i) {
+                const double a = (double)Dj * (double)e->inv_freq_h[i];
+                T.c[j][i] = (float)cos(a);
+                T.s[j][i] = (float)sin(a);
+            }
+        }
+        T.w[n_seg] = nl;
+        // sources end where the last segment's do: at len, or at the start of a last range that reaches len
+        const int64_t src_end = nl + Dj;
+        hipStream_t st = (hipStream_t)stream;
+        HIP_TRY(hipMemcpyAsync(e->evict_dev + k, &T, sizeof(KvEvictTable), hipMemcpyHostToDevice, st));
+        const hipError_t he = kv_evict_ranges_launch(kv_geom(s), e->cfg.num_layers, e->evict_dev + k, n_seg, src_end, st);
+        if (he == hipErrorNotSupported) return fail(VLO_E_UNSUPPORTED, "session_evict_ranges: head_dim must be 64 or 128");
+        HIP_TRY(he);
+        HIP_TRY(hipEventRecord(e->evict_ev[k], st));
+        e->evict_used[k] = true;
+        e->evict_slot = (k + 1) % VLO_EVICT_SLOTS;
+    }
+    const size_t keep = (size_t)((nl + VLO_PAGE_TOKENS - 1) / VLO_PAGE_TOKENS);
+    if (keep < s->pages.size()) {
+        // as session_evict_shard: the pages go back only after the move and any queued kernel that still reads them have drained
+        HIP_TRY(hipDeviceSynchronize());
+        std::lock_guard<std::mutex> g(e->pool_mu);
+        while (s->pages.size() > keep) {
+            e->free_pages.push_back(s->pages.back());
+            s->pages.pop_back();
+        }
+    }
+    s->len = nl;                                 // has_logits stays, as in session_evict_shard
+    return VLO_OK;
+}
+
+int vlo_session_evict_ranges(vlo_session *s, const int64_t *ranges_host, int n, void *stream) {
+    if (!s) return fail(VLO_E_INVALID, "bad session_evict_ranges arguments");
+    if (s->e->tp_size > 1) return fail(VLO_E_STATE, "a tensor-parallel shard is evicted through vlo_tp_session_evict_ranges");
+    if (int prc = pending_refusal(s, "session_evict_ranges")) return prc;
+    if (s->e->cfg.kv_dtype != VLO_KV_BF16)
+        return fail(VLO_E_UNSUPPORTED, "session_evict_ranges: an fp8 KV pool is not re-rotated (every eviction would re-round the surviving keys to e4m3)");
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    if (int rc = evict_ranges_normalize(ranges_host, n, s->len, &ranges)) return rc;
+    return session_evict_ranges_shard(s, ranges, stream);
 }
 
 // device scratch of the test / micro-benchmark entry points: freed on every return path

@@ -155,6 +155,17 @@ hipError_t kv_copy_pages_launch(const KvPool &kv, const int *src_pt, const int *
 // arguments), V^T moved bit for bit.  Reads kv.page_table up to the page of token len - 1.
 struct KvEvictRot { float c[64], s[64]; };
 hipError_t kv_evict_launch(const KvPool &kv, int layers, int64_t t0, int64_t d, int64_t len, const KvEvictRot &rot, hipStream_t st);
+// vlo_session_evict_ranges on a bf16 pool (head_dim 64 or 128): n_seg survivor runs move down in ONE pass.  Segment j < n_seg is destination
+// tokens [w[j], w[j + 1]) (ascending, non-empty; w[n_seg] = the new length), each read from w + D[j] (1 <= D[0] < D[1] < ..., w[n_seg] +
+// D[n_seg - 1] = len) with K rotated back by D[j] positions: c[j][i], s[j][i] = (float)cos, (float)sin of (double)D[j] * inv_freq[i],
+// i < head_dim / 2 — kv_evict_launch's arithmetic, so n_seg = 1 gives its result bit for bit.  V^T moves bit for bit; tokens below w[0] are
+// untouched.  `tab_dev` is DEVICE memory that stays valid and unchanged until the kernel has run.
+#define VLO_EVICT_MAX_RANGES 64      // = include/vlo.h
+struct KvEvictTable {
+    long long w[VLO_EVICT_MAX_RANGES + 1], D[VLO_EVICT_MAX_RANGES];
+    float c[VLO_EVICT_MAX_RANGES][64], s[VLO_EVICT_MAX_RANGES][64];
+};
+hipError_t kv_evict_ranges_launch(const KvPool &kv, int layers, const KvEvictTable *tab_dev, int n_seg, int64_t len, hipStream_t st);
 // per-row logit statistics, see llm_ops.hip
 hipError_t logit_rows_launch(const unsigned short *logits, int n, int V, int64_t ld, const int64_t *labels, int interval_id, float *lse,
                              int64_t *amax, float *label_logit, float *p_interval, int64_t *p_amax, hipStream_t st);

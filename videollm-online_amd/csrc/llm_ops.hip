@@ -1074,6 +1074,201 @@ hipError_t kv_evict_launch(const KvPool &kv, int layers, int64_t t0, int64_t d, 
     return hipGetLastError();
 }
 
+// vlo_session_evict_ranges: forget R disjoint ranges [a_j, b_j) of a bf16 pool in ONE pass.  The survivors keep their order; the run between
+// range j and range j + 1 is SEGMENT j: destination tokens [w_j, w_{j+1}) (w_0 = a_0, w_R = the new length), all moved down by the same
+// D_j = sum_{i <= j} (b_i - a_i), their keys rotated back by D_j positions with row j of the (c, s) table (rounded once, whatever R is), V^T
+// shifted bit for bit.  The table {w, D, c, s} is device memory (64 x 128 floats do not fit in kernel arguments); a block copies w, D and
+// — K blocks — its rows of (c, s) into LDS first.
+// The decomposition and the hazard argument are kv_evict_kernel's: a block owns one (layer, kv head, K | 64-row V^T slice) and walks its
+// DESTINATION tokens in ascending chunks.  A destination token t of segment j reads token t + D_j, and D_j >= 1 is non-decreasing along the
+// tail, so a chunk [a, b) reads nothing below a + 1 (V^T: nothing below the aligned vector holding a, which starts at a: its first vector
+// (g + D_j) / 8 with g >= a a multiple of 8) — never what an EARLIER chunk stored, all of which lies below a.  It may read its own range:
+// every thread loads all the chunk needs into registers, __syncthreads(), then stores.  A later chunk reads from b + 1 (V^T: b) on, which the
+// stores of this chunk ([a, b)) cannot touch, so the loads of chunk c + 1 are issued before the stores of chunk c (one barrier per chunk).
+// Every item finds its segment by bisection of w in LDS (<= 6 steps); a thread's 4 items and their segment numbers are fixed-index registers.
+// V^T: a destination vector of 8 tokens wholly inside one segment is the funnel shift of two aligned source vectors with sh = D_j & 7; one
+// that straddles a segment boundary, w_0 or the new end is read and written element by element, only where its tokens are moved.  No element
+// is read at or beyond len, no page-table entry beyond the page of token len - 1.
+template <int HD>
+__global__ __launch_bounds__(256) void kv_evict_ranges_kernel(KvGeom kv, const KvEvictTable *__restrict__ tab, int R, long long len) {
+    constexpr int PT = VLO_PAGE_TOKENS, HH = HD / 2;
+    __shared__ long long sw[VLO_EVICT_MAX_RANGES + 1], sD[VLO_EVICT_MAX_RANGES];
+    __shared__ __attribute__((aligned(16))) float sc[VLO_EVICT_MAX_RANGES][HH];
+    __shared__ __attribute__((aligned(16))) float ss[VLO_EVICT_MAX_RANGES][HH];
+    const int tid = threadIdx.x;
+    const bool is_k = (int)blockIdx.x < kv.num_kv_heads;
+    for (int i = tid; i <= R; i += 256) sw[i] = tab->w[i];
+    for (int i = tid; i < R; i += 256) sD[i] = tab->D[i];
+    if (is_k)
+        for (int i = tid; i < R * HH; i += 256) {
+            sc[i / HH][i % HH] = tab->c[i / HH][i % HH];
+            ss[i / HH][i % HH] = tab->s[i / HH][i % HH];
+        }
+    __syncthreads();
+    const long long t0 = sw[0], nl = sw[R];                    // destination tokens are [t0, nl)
+    // the segment of destination token t, t0 <= t < nl: the largest j with w_j <= t
+    auto seg = [&](long long t) {
+        int lo = 0, hi = R;
+        while (hi - lo > 1) {
+            const int m = (lo + hi) >> 1;
+            if (sw[m] <= t) lo = m; else hi = m;
+        }
+        return lo;
+    };
+    const size_t lay = (size_t)blockIdx.y * kv.layer_stride;
+    const int *__restrict__ pt = kv.page_table;
+    const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+    if (is_k) {
+        // ---- K: whole token rows of one kv head.  item = (token, 16-byte unit u): pairs (8u + k, 8u + k + HD / 2), k < 8
+        constexpr int U = HD / 16, CT = 256 * EVICT_K_ITEMS / U, TS = 256 / U;
+        const int u = tid % U, tl = tid / U;
+        bf16_t *base = kv.k_pool + lay + (size_t)blockIdx.x * PT * HD + u * 8;
+        auto row = [&](long long t) { return base + (size_t)pt[t / PT] * kv.page_elems + (size_t)(t % PT) * HD; };
+        uint4 cl[EVICT_K_ITEMS], ch[EVICT_K_ITEMS], nxl[EVICT_K_ITEMS], nxh[EVICT_K_ITEMS];
+        int cj[EVICT_K_ITEMS], nj[EVICT_K_ITEMS];
+        auto load = [&](long long cs, uint4 *lo, uint4 *hi, int *sj) {
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) {
+                const long long t = cs + tl + i * TS;
+                lo[i] = hi[i] = z4;
+                sj[i] = 0;
+                if (t >= t0 && t < nl) {
+                    const int j = seg(t);
+                    const bf16_t *src = row(t + sD[j]);
+                    lo[i] = *reinterpret_cast<const uint4 *>(src);
+                    hi[i] = *reinterpret_cast<const uint4 *>(src + HH);
+                    sj[i] = j;
+                }
+            }
+        };
+        long long cs = t0 / CT * CT;
+        load(cs, cl, ch, cj);
+        for (; cs < nl; cs += CT) {
+            if (cs + CT < nl) load(cs + CT, nxl, nxh, nj);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) {
+                const long long t = cs + tl + i * TS;
+                if (t >= t0 && t < nl) {
+                    const float4 *pc = reinterpret_cast<const float4 *>(&sc[cj[i]][u * 8]), *ps = reinterpret_cast<const float4 *>(&ss[cj[i]][u * 8]);
+                    const float4 c0 = pc[0], c1 = pc[1], s0 = ps[0], s1 = ps[1];
+                    const float c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+                    const unsigned lw[4] = {cl[i].x, cl[i].y, cl[i].z, cl[i].w}, hw[4] = {ch[i].x, ch[i].y, ch[i].z, ch[i].w};
+                    unsigned ol[4], oh[4];
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        // kv_evict_kernel's arithmetic, evaluated as written: two rounded fp32 products, one rounded sum, never a fused multiply-add
+#pragma clang fp contract(off)
+                        const float a0 = __uint_as_float(lw[w] << 16), a1 = __uint_as_float(lw[w] & 0xffff0000u);
+                        const float b0 = __uint_as_float(hw[w] << 16), b1 = __uint_as_float(hw[w] & 0xffff0000u);
+                        const float e0 = c[2 * w], e1 = c[2 * w + 1], f0 = s[2 * w], f1 = s[2 * w + 1];
+                        ol[w] = pack2bf(a0 * e0 + b0 * f0, a1 * e1 + b1 * f1);
+                        oh[w] = pack2bf(b0 * e0 - a0 * f0, b1 * e1 - a1 * f1);
+                    }
+                    bf16_t *dst = row(t);
+                    *reinterpret_cast<uint4 *>(dst) = make_uint4(ol[0], ol[1], ol[2], ol[3]);
+                    *reinterpret_cast<uint4 *>(dst + HH) = make_uint4(oh[0], oh[1], oh[2], oh[3]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < EVICT_K_ITEMS; ++i) { cl[i] = nxl[i]; ch[i] = nxh[i]; cj[i] = nj[i]; }
+        }
+        return;
+    }
+    // ---- V^T: 64 hd rows of one kv head, the token axis contiguous.  item = (hd row, aligned destination vector of 8 tokens starting at g)
+    const int vs = (int)blockIdx.x - kv.num_kv_heads;
+    const int head = vs / (HD / 64), r0 = vs % (HD / 64) * 64;
+    constexpr int VR = 256 * EVICT_V_ITEMS / 64, CV = VR * 8;   // vectors per row and tokens of a chunk
+    constexpr int ELEMENTWISE = 8;                              // the mode of a straddling vector (a whole one carries its sh = D_j & 7 < 8)
+    bf16_t *base = kv.vt_pool + lay + ((size_t)head * HD + r0) * PT;
+    // address of the aligned vector with GLOBAL index A (tokens 8A .. 8A + 7) of row r
+    auto vec = [&](long long A, int r) { return reinterpret_cast<uint4 *>(base + (size_t)pt[A / (PT / 8)] * kv.page_elems + (size_t)r * PT) + A % (PT / 8); };
+    uint4 ca[EVICT_V_ITEMS], cb[EVICT_V_ITEMS], na[EVICT_V_ITEMS], nb[EVICT_V_ITEMS];
+    int cm[EVICT_V_ITEMS], nm[EVICT_V_ITEMS];
+    auto load = [&](long long cs, uint4 *a, uint4 *b, int *mode) {
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) {
+            const int idx = tid + 256 * i, r = idx / VR;
+            const long long g = cs + (idx % VR) * 8;
+            a[i] = b[i] = z4;
+            mode[i] = 0;
+            if (g + 8 > t0 && g < nl) {                        // some destination token of the vector is moved
+                int j = seg(g > t0 ? g : t0);
+                if (g >= sw[j] && g + 8 <= sw[j + 1]) {        // wholly inside segment j: tokens g + D_j .. g + D_j + 7 < len
+                    const long long D = sD[j], A = (g + D) >> 3;
+                    a[i] = *vec(A, r);
+                    if ((D & 7) && (A + 1) * 8 < len) b[i] = *vec(A + 1, r);
+                    mode[i] = (int)(D & 7);
+                } else {                                       // straddles a boundary: the moved tokens one by one, each from its own segment
+                    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const long long t = g + k;
+                        if (t >= t0 && t < nl) {
+                            while (t >= sw[j + 1]) ++j;        // t < nl = w_R: ends at j <= R - 1
+                            const long long src = t + sD[j];   // < len
+                            const bf16_t v = base[(size_t)pt[src / PT] * kv.page_elems + (size_t)r * PT + src % PT];
+                            w[k >> 1] |= (unsigned)v << ((k & 1) * 16);
+                        }
+                    }
+                    a[i] = make_uint4(w[0], w[1], w[2], w[3]);
+                    mode[i] = ELEMENTWISE;
+                }
+            }
+        }
+    };
+    long long cs = t0 / CV * CV;
+    load(cs, ca, cb, cm);
+    for (; cs < nl; cs += CV) {
+        if (cs + CV < nl) load(cs + CV, na, nb, nm);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) {
+            const int idx = tid + 256 * i;
+            const long long g = cs + (idx % VR) * 8;
+            if (g + 8 > t0 && g < nl) {
+                unsigned w[8] = {ca[i].x, ca[i].y, ca[i].z, ca[i].w, cb[i].x, cb[i].y, cb[i].z, cb[i].w};
+                uint4 *dst = vec(g >> 3, idx / VR);
+                if (cm[i] != ELEMENTWISE) {
+                    const int sh = cm[i];
+                    if (sh & 4) {
+#pragma unroll
+                        for (int m = 0; m < 6; ++m) w[m] = w[m + 2];
+                    }
+                    if (sh & 2) {
+#pragma unroll
+                        for (int m = 0; m < 5; ++m) w[m] = w[m + 1];
+                    }
+                    if (sh & 1) {
+#pragma unroll
+                        for (int m = 0; m < 4; ++m) w[m] = (w[m] >> 16) | (w[m + 1] << 16);
+                    }
+                    *dst = make_uint4(w[0], w[1], w[2], w[3]);
+                } else {                                       // only the moved tokens are written
+                    bf16_t *d16 = reinterpret_cast<bf16_t *>(dst);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (g + k >= t0 && g + k < nl) d16[k] = (bf16_t)(w[k >> 1] >> ((k & 1) * 16));
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < EVICT_V_ITEMS; ++i) { ca[i] = na[i]; cb[i] = nb[i]; cm[i] = nm[i]; }
+    }
+}
+hipError_t kv_evict_ranges_launch(const KvPool &kv, int layers, const KvEvictTable *tab_dev, int n_seg, int64_t len, hipStream_t st) {
+    if (kv.dtype != VLO_KV_BF16) return hipErrorNotSupported;
+    if (!tab_dev || n_seg < 1 || n_seg > VLO_EVICT_MAX_RANGES) return hipErrorInvalidValue;
+    const KvGeom &g = kv;
+    if (kv.head_dim == 128)
+        hipLaunchKernelGGL(kv_evict_ranges_kernel<128>, dim3(kv.num_kv_heads * 3, layers), dim3(256), 0, st, g, tab_dev, n_seg, (long long)len);
+    else if (kv.head_dim == 64)
+        hipLaunchKernelGGL(kv_evict_ranges_kernel<64>, dim3(kv.num_kv_heads * 2, layers), dim3(256), 0, st, g, tab_dev, n_seg, (long long)len);
+    else
+        return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
 // Per-row statistics of a bf16 logits matrix [n][ld] (one block per row): everything stream_evaluate reads from the
 // logits (models/modeling_live.py:95-97, 107-112, 140-144) without materialising softmax rows:
 //   lse[r]          log sum exp (fp32)                  -> cross entropy = lse - label_logit

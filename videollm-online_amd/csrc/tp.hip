@@ -331,6 +331,18 @@ int vlo_tp_session_evict(vlo_tp_session *t, int64_t t0, int64_t t1, void *stream
     }
     return VLO_OK;
 }
+int vlo_tp_session_evict_ranges(vlo_tp_session *t, const int64_t *ranges_host, int n, void *stream) {
+    if (!t) return vlo_fail(VLO_E_INVALID, "bad tp_session_evict_ranges arguments");
+    for (vlo_session *s : t->ss)
+        if (s->e->cfg.kv_dtype != VLO_KV_BF16) return vlo_fail(VLO_E_UNSUPPORTED, "tp_session_evict_ranges: an fp8 KV pool is not re-rotated");
+    std::vector<std::pair<int64_t, int64_t>> ranges;
+    if (int rc = evict_ranges_normalize(ranges_host, n, vlo_tp_session_len(t), &ranges)) return rc;
+    for (vlo_session *s : t->ss) {               // checked above: no shard fails on its arguments after another has moved
+        const int rc = session_evict_ranges_shard(s, ranges, stream);
+        if (rc) return rc;
+    }
+    return VLO_OK;
+}
 
 // ---- p2p exchange ------------------------------------------------------------------------------------------------
 // Every rank owns a MAILBOX in its own HBM, mapped by every peer (hipIpc across processes, plain pointers inside one):

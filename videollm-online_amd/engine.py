@@ -86,6 +86,15 @@ def _ptr(t: torch.Tensor):
     return C.c_void_p(t.data_ptr())
 
 
+def _ranges_array(ranges):
+    """[(a, b), ...] -> (int64 [n][2] host array, n) for vlo_session_evict_ranges"""
+    ranges = [tuple(r) for r in ranges]
+    flat = [int(v) for r in ranges for v in r]
+    if len(flat) != 2 * len(ranges):
+        raise ValueError("evict_ranges takes (a, b) pairs")
+    return (C.c_int64 * max(len(flat), 1))(*flat), len(ranges)
+
+
 class Session:
     """KV handle: what the reference passes around as `past_key_values` (a DynamicCache).
     Truthiness and get_seq_length() match the uses in demo/inference.py:61,98."""
@@ -137,6 +146,13 @@ class Session:
         """Forget cache positions [t0, t1) in place: the tail moves down by t1 - t0 slots with its keys re-rotated by as many positions
         (include/vlo.h vlo_session_evict), so the length is again the next position.  Ordered on ``stream``; bf16 KV pools only."""
         _C.check(_C.lib().vlo_session_evict(self._h, t0, t1, _stream_handle(stream)))
+
+    def evict_ranges(self, ranges, stream=None):
+        """Forget several cache ranges ``[(a, b), ...]`` (coordinates before the call; ascending, non-overlapping, at most 64 after touching
+        ones are merged) in ONE pass: the cache is compacted once and every surviving key is re-rotated, and rounded, once by the number of
+        evicted positions below it (include/vlo.h vlo_session_evict_ranges).  Ordered on ``stream``; bf16 KV pools only."""
+        arr, n = _ranges_array(ranges)
+        _C.check(_C.lib().vlo_session_evict_ranges(self._h, arr, n, _stream_handle(stream)))
 
     def stream_steps(self, embeds: torch.Tensor, unit_ends: list, threshold: float, interval_id: int, tok_out: torch.Tensor,
                      p_out: torch.Tensor | None, accept_out: torch.Tensor, stream=None):
@@ -593,6 +609,11 @@ class TpSession:
     def evict(self, t0: int, t1: int, stream=None):
         """Forget cache positions [t0, t1) in place on every local KV shard (vlo_session_evict per shard)."""
         _C.check(_C.lib().vlo_tp_session_evict(self._h, t0, t1, _stream_handle(stream)))
+
+    def evict_ranges(self, ranges, stream=None):
+        """Forget several cache ranges in one pass on every local KV shard (vlo_session_evict_ranges per shard)."""
+        arr, n = _ranges_array(ranges)
+        _C.check(_C.lib().vlo_tp_session_evict_ranges(self._h, arr, n, _stream_handle(stream)))
 
 
 class TpGroup:

@@ -34,6 +34,7 @@ LOOKAHEAD_MAX_UNITS = 16   # frames of one lookahead pass (include/vlo.h vlo_str
 LOOKAHEAD_MAX_ROWS = 64    # rows of one lookahead pass (csrc VLO_BLOCK_TOKENS)
 LOOKAHEAD_IDS_MAX = 32     # ids the first unit of vlo_steps_input can carry
 KV_PAGE_TOKENS = 256       # tokens of one KV page (csrc/llm_ops.h VLO_PAGE_TOKENS): the hysteresis of KvBudget
+KV_EVICT_MAX_RANGES = 64   # ranges of one evict_ranges call (include/vlo.h VLO_EVICT_MAX_RANGES)
 
 
 class KvBudget:
@@ -44,9 +45,26 @@ class KvBudget:
     the sink is one SPAN.  ``enforce(cache, stream)`` — after a step or a response — does nothing while ``len(cache) <= budget``;
     else it pops whole oldest spans until the length is at most ``budget - KV_PAGE_TOKENS`` (one page of hysteresis: an eviction
     moves the whole tail, so it should be rare), never the newest span, and issues ONE ``cache.evict(sink, sink + d, stream)``.
-    Returns (t0, t1) of the eviction or None."""
+    Returns (t0, t1) of the eviction or None.
 
-    def __init__(self, budget: int, sink: int, max_span: int):
+    ``policy="frames_first"`` drops old FRAMES before any dialogue text (a standing request and the assistant's earlier answers outlive
+    the frames around them).  ``note_step(L0, n, lead, frame_tokens, interval_id)`` then also records each step's structure as PIECES in
+    cache order: a frame step (``lead`` = the ids in front of its ``frame_tokens`` frame rows) is a *frame* piece — the frame rows, and the
+    lead when it is exactly ``[interval_id]``, all a silent continuation carries — behind a *text* piece for any other lead; every other
+    step (query ids, generation prompt, response tokens) is one *text* piece.  ``enforce_ranges(cache, stream)``, once ``len > budget``,
+    takes the oldest frame pieces until the length is at most ``budget - KV_PAGE_TOKENS``, then — only if the frames ran out — the oldest
+    text pieces, never a piece of the newest step; adjacent pieces merge into ranges and go out as ONE ``cache.evict_ranges`` (include/vlo.h
+    vlo_session_evict_ranges: one compaction, every surviving key rounded once), or one per KV_EVICT_MAX_RANGES ranges.  Returns
+    [(t0, t1, length after that call)] per range, ascending, in the coordinates before its call."""
+
+    POLICIES = ("oldest", "frames_first")
+
+    def __init__(self, budget: int, sink: int, max_span: int, policy: str = "oldest"):
+        if policy not in self.POLICIES:
+            raise ValueError(f"kv_policy must be one of {self.POLICIES}, got {policy!r}")
+        self.policy = policy
+        self.pieces = []                   # frames_first: [is_frame, tokens, step number] past the sink, in cache order
+        self._step_no = 0
         budget, sink = int(budget), int(sink)
         if sink < 0:
             raise ValueError(f"kv_sink must be >= 0, got {sink}")
@@ -59,11 +77,27 @@ class KvBudget:
 
     def clear(self):
         self.spans.clear()
+        self.pieces.clear()
 
-    def note_step(self, L0: int, n: int):
-        span = L0 + n - max(L0, self.sink)
-        if span > 0:
-            self.spans.append(span)
+    def note_step(self, L0: int, n: int, lead=None, frame_tokens: int = 0, interval_id=None):
+        if self.policy == "oldest":
+            span = L0 + n - max(L0, self.sink)
+            if span > 0:
+                self.spans.append(span)
+            return
+        self._step_no += 1
+        if lead is None:                                   # a text step
+            parts = [(False, n)]
+        elif list(lead) == [interval_id]:                  # a silent continuation: the interval id belongs to its frame
+            parts = [(True, n)]
+        else:
+            parts = [(False, n - frame_tokens), (True, frame_tokens)]
+        p = L0
+        for is_frame, m in parts:
+            m2 = p + m - max(p, self.sink)                 # what lies past the sink
+            if m2 > 0:
+                self.pieces.append([is_frame, m2, self._step_no])
+            p += m
 
     def enforce(self, cache, stream=None):
         L = len(cache)
@@ -78,12 +112,49 @@ class KvBudget:
         self.evictions += 1
         return self.sink, self.sink + d
 
+    def enforce_ranges(self, cache, stream=None):
+        L = len(cache)
+        if L <= self.budget or not self.pieces:
+            return []
+        target, newest = self.budget - KV_PAGE_TOKENS, self.pieces[-1][2]
+        take, d = set(), 0
+        for frames in (True, False):                       # the oldest frames first; text only when the frames have run out
+            for i, (is_frame, m, step) in enumerate(self.pieces):
+                if L - d <= target:
+                    break
+                if is_frame == frames and step != newest:
+                    take.add(i)
+                    d += m
+        if not take:
+            return []
+        ranges, p = [], self.sink
+        for i, (_, m, _) in enumerate(self.pieces):
+            if i in take:
+                if ranges and ranges[-1][1] == p:
+                    ranges[-1][1] = p + m
+                else:
+                    ranges.append([p, p + m])
+            p += m
+        self.pieces = [pc for i, pc in enumerate(self.pieces) if i not in take]
+        out, gone = [], 0
+        for c in range(0, len(ranges), KV_EVICT_MAX_RANGES):
+            call = [(a - gone, b - gone) for a, b in ranges[c:c + KV_EVICT_MAX_RANGES]]   # the coordinates before THIS call
+            cache.evict_ranges(call, stream=stream)
+            self.evictions += 1
+            gone += sum(b - a for a, b in call)
+            out += [(a, b, L - gone) for a, b in call]
+        return out
+
 
 class LiveInfer:
     def __init__(self, model: LiveModel, tokens: StreamTokens | None = None, tokenizer=None, frame_fps: float = 2,
                  system_prompt: str = "", prefetch: bool = True, prefetch_frames: int = 2, schedule=None,
                  max_new_tokens: int = 100, record: int = 65536, encode_stream=None, kv_budget: int | None = None,
-                 kv_sink: int | None = None, lookahead: int = 1):
+                 kv_sink: int | None = None, lookahead: int = 1, kv_policy: str | None = None):
+        if kv_policy is not None and kv_policy not in KvBudget.POLICIES:
+            raise ValueError(f"kv_policy must be one of {KvBudget.POLICIES}, got {kv_policy!r}")
+        if kv_policy is not None and kv_budget is None:
+            raise ValueError("kv_policy without kv_budget")
         self.model = model
         self.engine = model.engine
         self.tokenizer = tokenizer
@@ -153,7 +224,10 @@ class LiveInfer:
         self._kv_budget = None
         if kv_budget is not None:
             longest_step = 1 + len(self._added_stream_prompt_ids) + self.frame_num_tokens   # [eos] + stream prompt + the frame
-            self._kv_budget = KvBudget(kv_budget, len(self._start_ids) if kv_sink is None else kv_sink, longest_step)
+            # kv_policy: what leaves first once the budget is crossed.  "oldest" (the default): the oldest steps, whatever they are;
+            # "frames_first": the oldest frames, dialogue text only when no frame is left (KvBudget)
+            self._kv_budget = KvBudget(kv_budget, len(self._start_ids) if kv_sink is None else kv_sink, longest_step,
+                                       "oldest" if kv_policy is None else kv_policy)
         elif kv_sink is not None:
             raise ValueError("kv_sink without kv_budget")
         self.past_key_values = None
@@ -190,16 +264,27 @@ class LiveInfer:
         if self._kv_budget is not None:
             self._kv_budget.clear()
 
-    def _log_step(self, Lc, n):
+    def _log_step(self, Lc, n, lead=None):
+        """``lead``: the ids a FRAME step carries in front of its frame rows (None: a step of text rows only)"""
         self.steps_total += 1
         if self._record:
             self.step_log.append((Lc, n))
         if self._kv_budget is not None:
-            self._kv_budget.note_step(Lc, n)
+            if self._kv_budget.policy == "oldest":
+                self._kv_budget.note_step(Lc, n)
+            else:
+                self._kv_budget.note_step(Lc, n, lead, self.frame_num_tokens, self.frame_token_interval_id)
 
     def _enforce_kv_budget(self, video_time):
         """After a step or a response: one eviction on the main stream when the cache is over its budget (KvBudget)."""
         if self._kv_budget is None:
+            return
+        if self._kv_budget.policy != "oldest":
+            with stage("evict"):
+                evs = self._kv_budget.enforce_ranges(self.past_key_values, self._main)
+            if self._record:
+                for t0, t1, kv_len in evs:             # one event per range, ascending, in the coordinates before its call
+                    self.trace.append(evict_event(video_time, t0, t1, kv_len))
             return
         with stage("evict"):
             ev = self._kv_budget.enforce(self.past_key_values, self._main)
@@ -369,7 +454,7 @@ class LiveInfer:
                                       device=self.model.device)
         with stage("step"):
             inputs_embeds = eng.step_input(self.last_ids, frame_embeds, self._stage)      # :61-68 without torch.tensor / torch.cat
-            self._log_step(len(self.past_key_values), inputs_embeds.shape[0])
+            self._log_step(len(self.past_key_values), inputs_embeds.shape[0], lead=self.last_ids)
             eng.llm_step(self.past_key_values, inputs_embeds, want_last=False)
         self._frames_done += 1
         self._prefetch_next()
@@ -469,7 +554,7 @@ class LiveInfer:
         video_time = None
         for j in range(keep):
             video_time = units[j][0]
-            self._log_step(L0 + (ends[j - 1] + 1 if j else 0), len(ids[j]) + T)
+            self._log_step(L0 + (ends[j - 1] + 1 if j else 0), len(ids[j]) + T, lead=ids[j])
             self._frames_done += 1
             if answer_after and j == n - 1:
                 break
